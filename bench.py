@@ -1,13 +1,17 @@
 """bench.py - denoising steps/sec of the DDIM / 3-D U-Net hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype bf16|f16] [--only 320x512|576x1024]
+    python bench.py --gpus N --steps K --warmup W [--dtype bf16|f16] [--only 320x512|576x1024] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one DDIM step of a 16-frame clip with classifier-free guidance = 2 U-Net forwards
 (25.2 TFLOP at 320x512, 104.7 TFLOP at 576x1024) + the fused update kernel.  Inputs (latent, contexts,
-weights) are synthetic (seeded) and resident in HBM before the timed region.  ONE run measures BOTH
-BASELINE resolutions on the same 1.44 B-parameter U-Net: the headline line (`value`, `ms_per_step`) is
-BASELINE configs[1] (320x512), `res_576x1024` carries configs[2].  Prints ONE JSON line on rank 0; extra
-objects:
+weights, the DDIM noise) are synthetic (seeded) and resident in HBM before the timed region.  The headline
+line (`value`, `ms_per_step`) is BASELINE configs[1] (320x512).  A plain run sets up, warms up, times the K
+steps and prints ONE JSON line on rank 0, nothing else.
+
+--full   also measures BASELINE configs[2] on the same 1.44 B-parameter U-Net (`res_576x1024`), the
+         first-stage decode, and the extra objects below (`--cpu-baseline off`, `--emulate-shard off`,
+         `--parity-mode off` drop single legs of it):
   roofline            the kernel family with the largest share of the 320x512 step (chosen from the live
                       measurement, not hard-coded), timed launch by launch with HIP events on the launch stream
                       during eagerly issued steps of the same loop (the timed steps replay a HIP graph, whose
@@ -22,6 +26,10 @@ objects:
 `other`); the timed steps replay a two-stream graph and are shorter than that sum.  `roofline.traffic` comes from the
 committed PMC summary (profiles/r04/pmc_traffic.json, separate rocprofv3 --pmc passes) only when that file was
 produced with the library sources of this run (digest match), else null - never a stale constant.
+
+--dump-outputs DIR   after the timed steps, writes what the last timed step handed back - the latent x_{t-1} that
+                     DDIMSampler.p_sample_ddim returns (rank 0's frame shard when N > 1) - as DIR/x_prev.npy (float32),
+                     so that two builds can be compared output for output on the same arguments.
 """
 import argparse
 import json
@@ -486,11 +494,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--only", default=None, choices=[None, "320x512", "576x1024"],
-                    help="kernel-work runs: measure one resolution (the driver line always carries both)")
+                    help="kernel-work runs: measure one resolution (a --full line carries both)")
     ap.add_argument("--res", default=None, help=argparse.SUPPRESS)  # (round-1 spelling of --only)
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: 576x1024, first-stage decode, roofline / per-kernel figures, attention ceiling, "
+                         "fp8 attention, compute_scaling, parity_mode, cpu_baseline (the 'auto' legs below)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the latent the last timed step returned to DIR/x_prev.npy (float32)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"], help="with --full")
     ap.add_argument("--emulate-shard", default="auto", choices=["auto", "off", "only"],
-                    help="compute_scaling: the U-Net forward on 16/N-frame clips (N = 2, 4, 8) on this one GPU; "
+                    help="compute_scaling (with --full): the U-Net forward on 16/N-frame clips (N = 2, 4, 8) on this one GPU; "
                          "'only' prints just that object")
     ap.add_argument("--fp8-attention", action="store_true",
                     help="spatial self-attention on pm_attention_fp8 (block-scaled e4m3 MFMA): BASELINE configs[4]")
@@ -502,7 +515,7 @@ def main():
                          "ops they feed) - the configuration whose FRAMES meet the north-star's 1e-3 (tests/test_frames_gpu.py); "
                          "use with --dtype f16: its step time goes on record next to the bf16 production number")
     ap.add_argument("--parity-mode", default="auto", choices=["auto", "off"],
-                    help="default run at 1 GPU: also the f16 selective-parity configuration - step time + FRAMES error against "
+                    help="--full run at 1 GPU: also the f16 selective-parity configuration - step time + FRAMES error against "
                          "the committed reference fixture - as `parity_mode` (the contract-conformant number beside the bf16 one)")
     ap.add_argument("--split", default="hybrid", choices=["hybrid", "frames-kv"],
                     help="N > 1: 'hybrid' = cond / uncond branch pair x N/2 frame shards, temporal blocks re-sharded frames <-> pixels "
@@ -556,6 +569,8 @@ def main():
         # both partners of a CFG pair must draw the same DDIM noise for their (shared) frame shard
         torch.manual_seed(1234 + (0 if fp is None else fp.rank))
         torch.cuda.manual_seed(1234 + (0 if fp is None else fp.rank))
+    else:
+        torch.manual_seed(1234)  # the DDIM noise (eta 1.0): the same arguments draw the same noise run to run
 
     def barrier():
         if world > 1:
@@ -578,7 +593,7 @@ def main():
         print(json.dumps({"compute_scaling": compute_scaling(pm_of, unet, ops, dev), "dtype": a.dtype}), flush=True)
         return
 
-    def run_resolution(res, steps, warmup):
+    def run_resolution(res, steps, warmup, full):
         h, w = factory.RESOLUTIONS[res]["image_size"]
         pm = pm_of(res)
         ins = synth.synth_inputs(h, w, T, seed=123)
@@ -610,68 +625,72 @@ def main():
         run(steps, warmup)
         barrier()
         elapsed = time.perf_counter() - t0
-        # Roofline leg: the timed steps replay a HIP graph (events cannot bracket nodes of a captured graph), so
-        # the kernel families are timed right after, live, with HIP events around every one of their launches on
-        # the launch stream during two more, eagerly launched steps of the same loop.
-        smp.use_graph = False
-        if fp is not None:
-            for k in fp.calls:
-                fp.calls[k] = 0
-        fwd_count = [0]
-        run(1, warmup + steps)
-        fwd_count[0] = 3 * (1 if cfgp is not None else 2)  # the 1 + 2 eager steps below, forwards per step on this rank
-        ops.reset()
-        ops.enabled = True
-        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s0.record()
-        run(2, warmup + steps + 1)
-        s1.record()
-        torch.cuda.synchronize()
-        ops.enabled = False
-        seq_step_ms = s0.elapsed_time(s1) / 2.0  # one eager, single-stream step (what the family times are parts of)
-        fams, big, kern, side = ops.summary()
+        # what the last timed step returned (--dump-outputs), before any untimed step below moves `x`
+        x_timed = x.detach().float().clone()
         if world > 1:
             tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
             elapsed = tt.item()
-        assert torch.isfinite(x).all(), "latent went non-finite"
+        assert torch.isfinite(x_timed).all(), "latent went non-finite"
         step_s = elapsed / steps
-        fam_out = {}
-        for k, v in fams.items():
-            tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0
-            tbs = v["bytes"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0
-            fam_out[k] = {"ms_per_step": v["ms"] / 2.0, "launches_per_step": v["launches"] // 2,
-                          "tflops": tf, "frac_of_peak": tf / MFMA_PEAK_TFLOPS,
-                          # the same launches against the OTHER roofline: algorithmic bytes (operands + output once)
-                          "algorithmic_TBps": tbs, "frac_of_hbm_8TBps": tbs / 8.0,
-                          # per-launch roofline: every launch priced at max(FLOPs / 2.5 PF, bytes / 8 TB/s)
-                          "frac_of_per_launch_roofline": (v["roofline_s"] / (v["ms"] * 1e-3)) if v["ms"] > 0 else 0.0,
-                          "share_of_sequential_step": (v["ms"] / 2.0) / seq_step_ms}
-        # the HBM-bound side kernels, family by family (their brackets exclude launches made from inside an MFMA-family op,
-        # e.g. conv3x3's own split16 pass, which stay in that family's time), then what is left: gaps of the eager issue
-        kern_ms = sum(v["ms"] for v in fams.values()) + sum(v["ms"] for v in side.values())
-        for k, v in side.items():
-            tbs = v["bytes"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0
-            fam_out[k] = {"ms_per_step": v["ms"] / 2.0, "launches_per_step": v["launches"] // 2, "bound": "hbm",
-                          "algorithmic_TBps": tbs, "frac_of_hbm_8TBps": tbs / 8.0, "kernel": SIDE[k],
-                          "share_of_sequential_step": (v["ms"] / 2.0) / seq_step_ms}
-        for k in fam_out:  # shares of the summed KERNEL time: independent of how the step's launches are issued / overlapped
-            fam_out[k]["share_of_kernel_time"] = fam_out[k]["ms_per_step"] * 2.0 / kern_ms
-        fam_out["gaps"] = {"ms_per_step": seq_step_ms - kern_ms / 2.0,
-                           "share_of_sequential_step": 1.0 - kern_ms / 2.0 / seq_step_ms,
-                           "what": "idle time between the launches of an eagerly issued, single-stream step (host issue + kernel "
-                                   "boundaries); the timed steps replay a two-stream HIP graph and do not pay it"}
-        fam_out["timed_step"] = {"ms_per_step": 1e3 * step_s, "kernel_ms_per_step": kern_ms / 2.0,
-                                 "what": "the headline step (graph replay, cond / uncond forwards on two streams) against the summed "
-                                         "kernel time of one step: < 1 means the two forwards overlap on the device",
-                                 "step_over_kernel_time": 1e3 * step_s / (kern_ms / 2.0)}
-        if fp is not None and multi_gpu is not None and "exchanges_per_forward" not in multi_gpu:
-            # the eager steps above walked the Python forward: 3 steps x forwards-per-step of this rank since the reset below
-            multi_gpu["exchanges_per_forward"] = {k: v / max(1, fwd_count[0]) for k, v in fp.calls.items()}
+        r = {"res": res, "latent": [T, h, w], "steps": steps, "elapsed": elapsed, "step_s": step_s, "x": x, "x_timed": x_timed,
+             "ins": ins}
+        if full:
+            # Roofline leg: the timed steps replay a HIP graph (events cannot bracket nodes of a captured graph), so
+            # the kernel families are timed right after, live, with HIP events around every one of their launches on
+            # the launch stream during two more, eagerly launched steps of the same loop.
+            smp.use_graph = False
+            if fp is not None:
+                for k in fp.calls:
+                    fp.calls[k] = 0
+            fwd_count = [0]
+            run(1, warmup + steps)
+            fwd_count[0] = 3 * (1 if cfgp is not None else 2)  # the 1 + 2 eager steps below, forwards per step on this rank
+            ops.reset()
+            ops.enabled = True
+            s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            run(2, warmup + steps + 1)
+            s1.record()
+            torch.cuda.synchronize()
+            ops.enabled = False
+            seq_step_ms = s0.elapsed_time(s1) / 2.0  # one eager, single-stream step (what the family times are parts of)
+            fams, big, kern, side = ops.summary()
+            fam_out = {}
+            for k, v in fams.items():
+                tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0
+                tbs = v["bytes"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0
+                fam_out[k] = {"ms_per_step": v["ms"] / 2.0, "launches_per_step": v["launches"] // 2,
+                              "tflops": tf, "frac_of_peak": tf / MFMA_PEAK_TFLOPS,
+                              # the same launches against the OTHER roofline: algorithmic bytes (operands + output once)
+                              "algorithmic_TBps": tbs, "frac_of_hbm_8TBps": tbs / 8.0,
+                              # per-launch roofline: every launch priced at max(FLOPs / 2.5 PF, bytes / 8 TB/s)
+                              "frac_of_per_launch_roofline": (v["roofline_s"] / (v["ms"] * 1e-3)) if v["ms"] > 0 else 0.0,
+                              "share_of_sequential_step": (v["ms"] / 2.0) / seq_step_ms}
+            # the HBM-bound side kernels, family by family (their brackets exclude launches made from inside an MFMA-family op,
+            # e.g. conv3x3's own split16 pass, which stay in that family's time), then what is left: gaps of the eager issue
+            kern_ms = sum(v["ms"] for v in fams.values()) + sum(v["ms"] for v in side.values())
+            for k, v in side.items():
+                tbs = v["bytes"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0
+                fam_out[k] = {"ms_per_step": v["ms"] / 2.0, "launches_per_step": v["launches"] // 2, "bound": "hbm",
+                              "algorithmic_TBps": tbs, "frac_of_hbm_8TBps": tbs / 8.0, "kernel": SIDE[k],
+                              "share_of_sequential_step": (v["ms"] / 2.0) / seq_step_ms}
+            for k in fam_out:  # shares of the summed KERNEL time: independent of how the step's launches are issued / overlapped
+                fam_out[k]["share_of_kernel_time"] = fam_out[k]["ms_per_step"] * 2.0 / kern_ms
+            fam_out["gaps"] = {"ms_per_step": seq_step_ms - kern_ms / 2.0,
+                               "share_of_sequential_step": 1.0 - kern_ms / 2.0 / seq_step_ms,
+                               "what": "idle time between the launches of an eagerly issued, single-stream step (host issue + kernel "
+                                       "boundaries); the timed steps replay a two-stream HIP graph and do not pay it"}
+            fam_out["timed_step"] = {"ms_per_step": 1e3 * step_s, "kernel_ms_per_step": kern_ms / 2.0,
+                                     "what": "the headline step (graph replay, cond / uncond forwards on two streams) against the summed "
+                                             "kernel time of one step: < 1 means the two forwards overlap on the device",
+                                     "step_over_kernel_time": 1e3 * step_s / (kern_ms / 2.0)}
+            if fp is not None and multi_gpu is not None and "exchanges_per_forward" not in multi_gpu:
+                # the eager steps above walked the Python forward: 3 steps x forwards-per-step of this rank since the reset below
+                multi_gpu["exchanges_per_forward"] = {k: v / max(1, fwd_count[0]) for k, v in fp.calls.items()}
+            r.update(seq_step_ms=seq_step_ms, families=fam_out, raw=fams, attn_big=big, kern=kern, x=x)
         smp.close()  # graphs (and the exchange buffers recorded between them) go before the process group does
-        return {"res": res, "latent": [T, h, w], "steps": steps, "elapsed": elapsed, "step_s": step_s,
-                "seq_step_ms": seq_step_ms, "families": fam_out, "raw": fams, "attn_big": big, "kern": kern, "x": x,
-                "ins": ins}
+        return r
 
     # N > 1: what the run actually was (VERDICT r03 #6b) - the ranks a real all-reduce saw, and the exchanges one rank's
     # forward issues, counted by FrameParallel during the warm-up / recording forwards of the first resolution
@@ -688,15 +707,19 @@ def main():
                              "driver computes efficiency from its own per-N runs"}
     results = {}
     if only in (None, "320x512"):
-        results["320x512"] = run_resolution("320x512", a.steps, a.warmup)
-    if only in (None, "576x1024"):
+        results["320x512"] = run_resolution("320x512", a.steps, a.warmup, a.full)
+    if only == "576x1024" or (only is None and a.full):
         s1024 = a.steps if only else max(3, min(a.steps, 10))
-        results["576x1024"] = run_resolution("576x1024", s1024, min(a.warmup, 2) if not only else a.warmup)
+        results["576x1024"] = run_resolution("576x1024", s1024, min(a.warmup, 2) if not only else a.warmup, a.full)
     head = results.get("320x512") or results["576x1024"]
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "x_prev.npy"), head["x_timed"].cpu().numpy())
 
     # first-stage decode of the clip (the step after the loop): reported beside the loop
     decode_ms = None
-    if world == 1 and "320x512" in results:
+    if a.full and world == 1 and "320x512" in results:
         from open_pandora_amd.autoencoder import AutoencoderKL
         h, w = head["latent"][1:]
         with torch.device("meta"):
@@ -790,14 +813,15 @@ def main():
             "config": {"workload": f"{res} (latent {T}x{head['latent'][1]}x{head['latent'][2]}), 16 frames, 50-step DDIM "
                                    f"schedule (eta 1.0, uniform_trailing), cfg 4.0 => 2 U-Net forwards/step, 1.44 B-parameter "
                                    f"U-Net = BASELINE configs[{1 if res == '320x512' else 2}]; the same run also measures "
-                                   f"{'576x1024 (configs[2]) -> res_576x1024' if only is None else 'only this resolution'}",
+                                   f"{'576x1024 (configs[2]) -> res_576x1024' if only is None and a.full else 'only this resolution'}",
                        "latent": head["latent"], "parallelism": mode},
             "sec_per_2s_video": 50.0 * head["step_s"],
             "ae_decode_ms_16_frames": decode_ms,
             "sec_per_2s_video_incl_decode": None if decode_ms is None else 50.0 * head["step_s"] + 1e-3 * decode_ms,
             "whole_step_mfma_frac": FLOP_PER_STEP[res] / head["step_s"] / 1e12 / MFMA_PEAK_TFLOPS / world,
-            "roofline": roof(head),
         }
+        if a.full:
+            out["roofline"] = roof(head)
         r2 = results.get("576x1024")
         if r2 is not None and r2 is not head:
             out["res_576x1024"] = {
@@ -805,7 +829,7 @@ def main():
                 "sec_per_2s_video": 50.0 * r2["step_s"], "latent": r2["latent"],
                 "whole_step_mfma_frac": FLOP_PER_STEP["576x1024"] / r2["step_s"] / 1e12 / MFMA_PEAK_TFLOPS / world,
                 "roofline": roof(r2)}
-        if r2 is not None and r2["attn_big"]["launches"]:
+        if a.full and r2 is not None and r2["attn_big"]["launches"]:
             b = r2["attn_big"]
             ach = b["flops"] / (b["ms"] * 1e-3) / 1e12
             out["roofline_attention"] = {
@@ -832,11 +856,11 @@ def main():
             out["config"]["attention"] = "fp8 (e4m3) operands on v_mfma_scale_f32_32x32x64_f8f6f4 for the spatial self-attention"
         if multi is not None:
             out["config4_multiround"] = multi
-        if a.emulate_shard == "auto" and world == 1 and only is None:
+        if a.full and a.emulate_shard == "auto" and world == 1 and only is None:
             out["compute_scaling"] = compute_scaling(pm_of, unet, ops, dev)
-        if a.parity_mode == "auto" and world == 1 and only is None and not a.rehearsal_width:
+        if a.full and a.parity_mode == "auto" and world == 1 and only is None and not a.rehearsal_width:
             out["parity_mode"] = parity_mode_leg(dev)
-        if a.cpu_baseline == "auto" and world == 1:
+        if a.full and a.cpu_baseline == "auto" and world == 1:
             out["cpu_baseline"] = cpu_baseline(unet, res, head["ins"])
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -36,7 +36,7 @@ def test_bench_gpus_8_rehearsal(split, bulk):
                OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--only", "320x512", "--rehearsal-width", "64", "--split", split]
+           "--only", "320x512", "--rehearsal-width", "64", "--split", split, "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1400)
     assert p.returncode == 0, p.stdout[-3000:] + "\n" + p.stderr[-6000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

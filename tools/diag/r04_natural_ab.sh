@@ -10,5 +10,5 @@ for res in 576x1024 320x512; do
   done
 done
 for v in 0 1 0 1; do
-  PANDORA_GEMM_NATURAL=$v timeout 300 python3 bench.py --steps 20 --warmup 5 --cpu-baseline off --emulate-shard off > $O/bench_nat${v}_$RANDOM.json 2>/dev/null
+  PANDORA_GEMM_NATURAL=$v timeout 300 python3 bench.py --steps 20 --warmup 5 --full --cpu-baseline off --emulate-shard off > $O/bench_nat${v}_$RANDOM.json 2>/dev/null
 done
