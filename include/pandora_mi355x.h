@@ -283,6 +283,49 @@ int pm_attention_generic(const void* q, int64_t q_bs, int64_t q_rs, const void* 
                          int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs, int64_t B, int64_t heads,
                          int64_t Nq, int64_t D, float scale, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MXFP8: OCP e4m3fn elements with one E8M0 (power-of-two) scale per 32 consecutive elements along K, for the projections of
+ * BasicTransformerBlock (opt-in, HipOps(fp8_linear=True)) on the block-scaled MFMA v_mfma_scale_f32_16x16x128_f8f6f4 (twice
+ * the bf16 rate; the scales are applied inside the instruction).  A quantised [M, K] tensor is an e4m3 byte matrix [M, K]
+ * (row stride ldq) plus E8M0 scale bytes [M, K/32] (row stride lds); value = e4m3(q) * 2^(scale - 127).
+ * Quantisation rule ("round the scale up": the block maximum is never clipped), per block of 32 values with amax a:
+ *   - X = clamp(ceil(log2(a / 448)), -127, 127); E8M0 code X + 127.  An all-zero block gets code 0.
+ *   - elements: v / 2^X rounded to nearest-even in e4m3fn, subnormals (steps of 2^-9) included; |v / 2^X| <= 448 by
+ *     construction, so nothing saturates.  Negative values that round to zero keep their sign (code 0x80).
+ *   - a block holding a NaN or an Inf: E8M0 code 0xFF and every element the e4m3 NaN 0x7F, so that every output it touches
+ *     is NaN.
+ * The same rule quantises weights (UNetModel.prepare, once) and activations (per call); tests/test_mx8_cpu.py restates it.
+ */
+#define PM_OUT_MX8 0x400 /* OR-ed into the `dtype` of pm_gemm_mx8: C is MXFP8 (e4m3 [M, Nout] + E8M0 scales [M, Nout/32] in Cs) */
+
+/* pm_quant_mx8: x [M, K] (in_dtype PM_F16 / PM_BF16 / PM_F32, row stride ldx) -> e4m3 q [M, K] (ldq) + scales [M, K/32] (lds).
+ *   plain (gamma == beta == NULL): the attention output in front of to_out (attention.py:144).
+ *   LayerNorm-fused (gamma, beta f32 [K], PM_F32 input = the residual stream, K <= 4096): quantises
+ *     (x - mean) * rsqrt(var + eps) * gamma + beta, computed in f32, in the same pass - norm1 / norm2 / norm3 of
+ *     BasicTransformerBlock._forward (attention.py:242-246) in front of the projections below; the 16-bit LayerNorm output
+ *     never goes to memory.
+ *   K % 32 == 0; ldx % 8 == 0 (f32: % 4 == 0), 16-byte aligned x; ldq % 8 == 0, 8-byte aligned q; lds >= K/32.
+ */
+int pm_quant_mx8(const void* x, int64_t ldx, const float* gamma, const float* beta, float eps, void* q, int64_t ldq,
+                 void* scales, int64_t lds, int64_t M, int64_t K, int in_dtype, void* stream);
+
+/* pm_gemm_mx8:  C[M, N] = epilogue(deq(Aq, As) · deq(Wq, Ws)^T), f32 accumulation, epilogue as pm_gemm.
+ * replaces the transformer-block projections in MXFP8 mode: to_q|k|v / to_q (attention.py:86-99), to_out (:144), the GEGLU
+ * projection and the output Linear of FeedForward (:415-440).
+ *   Aq e4m3 [M, K] (lda % 16 == 0), As [M, K/32]; Wq e4m3 [N, K] (ldw % 16 == 0), Ws [N, K/32]; 16-byte aligned bases.
+ *   flavours: bias (f32 [N], may be NULL) added; PM_FLAG_BIAS_IS_SCALE: bias multiplies column n (q|k|v with the softmax
+ *     prescale on q); PM_FLAG_OUT_F32: f32 C onto an f32 residual (the stream, to_out); PM_FLAG_RES_F32: 16-bit C, f32
+ *     residual (ff2); a residual of `dtype` without flags; PM_ACT_GEGLU (weights packed as for pm_gemm, N % 64 == 0,
+ *     no residual): 16-bit C [M, N/2], or with PM_OUT_MX8 in `dtype` an MXFP8 C (e4m3 [M, N/2], ldc bytes; scales Cs
+ *     [M, N/64], ldcs) ready to be ff2's A operand.
+ *   Any M; N % 32 == 0; K % 64 == 0 (K % 128 == 64 runs a zero-filled half step); ldc % 4 == 0.  Everything else -
+ *   PM_FLAG_A_F32, PM_FLAG_A_LO, PM_FLAG_W_WRAP, PM_FLAG_STATS_I64, column statistics, PM_OUT_HILO, other activations -
+ *   returns PM_E_SHAPE.
+ */
+int pm_gemm_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, int64_t ldw, const void* Ws,
+                int64_t ldws, const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, void* Cs, int64_t ldcs,
+                int64_t M, int64_t N, int64_t K, int act, int flags, int dtype, void* stream);
+
 /* (Diagnostics - kernel-variant overrides, ceiling probes, environment tuning switches - are NOT part of this library:
  * they exist only in the -DPM_DIAG build, libpandora_mi355x_diag.so, declared in include/pandora_mi355x_diag.h.  This
  * library reads no environment variable and has no mutable process-wide state.) */

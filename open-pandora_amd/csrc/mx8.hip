@@ -1,0 +1,487 @@
+// MXFP8 (OCP e4m3fn elements, one E8M0 power-of-two scale per 32 consecutive elements along K) for the projections of the
+// U-Net's transformer blocks: the quantiser pm_quant_mx8 (plain, or LayerNorm-fused on the f32 residual stream) and the
+// block-scaled GEMM pm_gemm_mx8 on v_mfma_scale_f32_16x16x128_f8f6f4 (K = 128 per instruction at twice the bf16 rate, the
+// scales applied inside the instruction).  Quantisation rule: include/pandora_mi355x.h, "MXFP8".
+#include "gemm_common.hpp"
+
+namespace pm {
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+
+// ---- the quantisation rule (restated in numpy by tests/test_mx8_cpu.py) --------------------------------------------------
+// Scale exponent of a block with amax a (finite): X = clamp(ceil(log2(a / 448)), -127, 127), exactly: a = 1.m * 2^e gives
+// X = e - 8 + (1.m > 1.75).  f32 subnormal a (and a = 0) give -127 (E8M0 code 0).
+__device__ __forceinline__ int mx8_exp(float amax) {
+  const uint32_t b = __float_as_uint(amax);
+  const int e = (int)((b >> 23) & 0xff);
+  if (e == 0) return -127;
+  const int X = e - 135 + ((b & 0x7fffff) > 0x600000u ? 1 : 0);
+  return X < -127 ? -127 : (X > 127 ? 127 : X);
+}
+// 2^-X as an f32 (X in [-127, 120] for finite inputs: always a normal number)
+__device__ __forceinline__ float mx8_inv_scale(int X) { return __uint_as_float((uint32_t)(127 - X) << 23); }
+// e4m3fn code of y (|y| <= 448, finite), round to nearest even, subnormals (steps of 2^-9) included.  In software so that the
+// result does not depend on the hardware converter's tie / subnormal handling.
+__device__ __forceinline__ uint32_t e4m3_rne(float y) {
+  uint32_t b = __float_as_uint(y);
+  const uint32_t s = (b >> 24) & 0x80u;
+  b &= 0x7fffffffu;
+  if (b >= 0x3c800000u) {  // |y| >= 2^-6: normal
+    b += 0x7ffffu + ((b >> 20) & 1u);
+    return s | (((b >> 23) - 120u) << 3) | ((b >> 20) & 7u);
+  }
+  return s | (uint32_t)__builtin_rintf(__uint_as_float(b) * 512.0f);  // 8 -> 0x08 = 2^-6, the smallest normal
+}
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e38f; }  // (false for NaN)
+
+// One block of 32 values spread over 4 lanes (8 each) that differ in lane-index bits O1 and O2: E8M0 code of the block and the
+// 8 e4m3 codes of this lane (two little-endian words).  A block holding a NaN or an Inf: code 0xFF and NaN (0x7F) elements.
+template <int O1, int O2>
+__device__ __forceinline__ uint32_t mx8_block(const float (&v)[8], uint32_t& w0, uint32_t& w1) {
+  float amax = 0.f;
+  int bad = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    amax = fmaxf(amax, fabsf(v[e]));
+    bad |= finite_f(v[e]) ? 0 : 1;
+  }
+  amax = fmaxf(amax, __shfl_xor(amax, O1, 64));
+  amax = fmaxf(amax, __shfl_xor(amax, O2, 64));
+  bad |= __shfl_xor(bad, O1, 64);
+  bad |= __shfl_xor(bad, O2, 64);
+  if (bad) {
+    w0 = w1 = 0x7f7f7f7fu;
+    return 0xffu;
+  }
+  const int X = mx8_exp(amax);
+  const float inv = mx8_inv_scale(X);
+  uint32_t c[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) c[e] = e4m3_rne(v[e] * inv);  // (exact product: a power of two, result >= 2^-126 or irrelevant)
+  w0 = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+  w1 = c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24);
+  return (uint32_t)(X + 127);
+}
+
+template <typename TI>
+__device__ __forceinline__ void load8(const TI* p, float (&v)[8]) {
+  Pack8<TI> t;
+  t.u = ld_global16(p);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = to_f32(t.e[e]);
+}
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = a[e];
+    v[4 + e] = b[e];
+  }
+}
+
+// ---- pm_quant_mx8: one wave per row, 8 consecutive elements per lane, a block = 4 adjacent lanes --------------------------
+constexpr int QMAX_IT = 8;  // LayerNorm mode keeps the row in registers: K <= 8 * 512 = 4096
+
+template <typename TI, bool LN>
+__global__ __launch_bounds__(256) void mx8_quant_kernel(const TI* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, float eps, uint8_t* __restrict__ q,
+                                                        int64_t ldq, uint8_t* __restrict__ s, int64_t lds, int M, int K) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const TI* xr = x + (int64_t)row * ldx;
+  uint8_t* qr = q + (int64_t)row * ldq;
+  uint8_t* sr = s + (int64_t)row * lds;
+  const int nit = (K + 511) >> 9;
+  if constexpr (!LN) {
+    for (int it = 0; it < nit; ++it) {
+      const int col = (it * 64 + lane) * 8;
+      float v[8];
+      if (col < K) {
+        load8(xr + col, v);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+      }
+      uint32_t w0, w1;
+      const uint32_t code = mx8_block<1, 2>(v, w0, w1);  // (K % 32 == 0: the 4 lanes of a block share one fate)
+      if (col < K) {
+        *reinterpret_cast<u32x2*>(qr + col) = u32x2{w0, w1};
+        if ((lane & 3) == 0) sr[col >> 5] = (uint8_t)code;
+      }
+    }
+  } else {
+    // LayerNorm as pm_layernorm computes it (mean, then the centred sum of squares, rsqrt(var + eps), * gamma + beta in f32),
+    // quantised from the f32 value: the 16-bit LayerNorm output never exists
+    float v[QMAX_IT][8];
+    float sum = 0.f;
+#pragma unroll
+    for (int it = 0; it < QMAX_IT; ++it) {
+      const int col = (it * 64 + lane) * 8;
+      if (it < nit && col < K) {
+        load8(xr + col, v[it]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = 0.f;
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sum += v[it][e];
+    }
+    const float mean = wave_sum(sum) / (float)K;
+    float ss = 0.f;
+#pragma unroll
+    for (int it = 0; it < QMAX_IT; ++it) {
+      const int col = (it * 64 + lane) * 8;
+      if (it < nit && col < K) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = v[it][e] - mean;
+          ss = fmaf(d, d, ss);
+        }
+      }
+    }
+    const float rstd = rsqrtf(wave_sum(ss) / (float)K + eps);
+#pragma unroll
+    for (int it = 0; it < QMAX_IT; ++it) {
+      if (it >= nit) break;
+      const int col = (it * 64 + lane) * 8;
+      float y[8];
+      if (col < K) {
+        float g[8], b[8];
+        load8(gamma + col, g);
+        load8(beta + col, b);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[e] = (v[it][e] - mean) * rstd * g[e] + b[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[e] = 0.f;
+      }
+      uint32_t w0, w1;
+      const uint32_t code = mx8_block<1, 2>(y, w0, w1);
+      if (col < K) {
+        *reinterpret_cast<u32x2*>(qr + col) = u32x2{w0, w1};
+        if ((lane & 3) == 0) sr[col >> 5] = (uint8_t)code;
+      }
+    }
+  }
+}
+
+// ---- pm_gemm_mx8 ------------------------------------------------------------------------------------------------------------
+// 128 x 128 output tile, 4 waves of 64 x 64 (acc[4][4] of 16x16 blocks), BK = 128 fp8 = the bytes of the bf16 kernels' BK = 64.
+// Both operands are staged through registers (one K-step ahead) into two LDS buffers of 128 rows x 128 bytes each, the 16-byte
+// chunks of a row XOR-swizzled by (row & 7); the zero-filled second half of the last K-step (K % 128 == 64) comes for free.
+// Operand map of v_mfma_scale_f32_16x16x128_f8f6f4 (tools/probes/mfma_scale16_layout.hip, exact integers with a different
+// scale per lane): lane l holds row l & 15 in two K = 64 halves - bytes 0..15 are k = 16 (l >> 4) + 0..15, bytes 16..31 are
+// k = 64 + 16 (l >> 4) + 0..15 - while its scale operand scales the 32-block k = 32 (l >> 4) .. +31 of that row (whose bytes
+// other lanes hold).  So a lane reads 16-byte chunks l >> 4 and 4 + (l >> 4) of its row and passes the scale of block l >> 4.  As in the bf16 kernels the MFMA computes C^T (W fragment as the instruction's A), so
+// lane (fr = l & 15, fq = l >> 4) accumulates row m = 16 i + fr, columns n = 16 j + 4 fq + r (r = 0..3) of block (i, j).
+constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 128;
+constexpr int MX_TILE = MX_BM * MX_BK;  // bytes per operand and buffer
+
+enum { MX_EPI_16 = 0, MX_EPI_F32 = 1, MX_EPI_GEGLU = 2, MX_EPI_GEGLU_MX = 3 };
+
+struct Mx8Params {
+  const uint8_t* A;
+  int64_t lda;
+  const uint8_t* As;
+  int64_t ldas;
+  const uint8_t* W;
+  int64_t ldw;
+  const uint8_t* Ws;
+  int64_t ldws;
+  const float* bias;
+  const void* R;
+  int64_t ldr;
+  void* C;
+  int64_t ldc;
+  uint8_t* Cs;
+  int64_t ldcs;
+  int M, N, K;
+  int bias_mul;  // PM_FLAG_BIAS_IS_SCALE
+  int res32;     // residual is f32
+  int mtiles, ntiles;
+};
+
+__device__ __forceinline__ int swz(int row, int chunk) { return row * MX_BK + ((chunk ^ (row & 7)) << 4); }
+
+template <typename T, int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(Mx8Params p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[2][2][MX_TILE];  // [buffer][A, W]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fq = lane >> 4;
+  const int nwg = p.mtiles * p.ntiles;
+  const int bid = xcd_remap(blockIdx.x, nwg);
+  const int mt = bid / p.ntiles, nt = bid - mt * p.ntiles;
+  const int m0 = mt * MX_BM, n0 = nt * MX_BN;
+  const int nk = (p.K + MX_BK - 1) / MX_BK;
+  const int kblocks = p.K >> 5;
+
+  // staging: chunk c = tid + 256 q (q = 0..3) of a tile is row c >> 3, 16-byte chunk c & 7
+  const uint8_t* ga[4];
+  const uint8_t* gw[4];
+  int lo[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int c = tid + 256 * q, row = c >> 3, ch = c & 7;
+    const int am = min(m0 + row, p.M - 1), wr = min(n0 + row, p.N - 1);  // (clamped rows: loaded, never stored)
+    ga[q] = p.A + (int64_t)am * p.lda + ch * 16;
+    gw[q] = p.W + (int64_t)wr * p.ldw + ch * 16;
+    lo[q] = swz(row, ch);
+  }
+  // scale rows of this lane's fragments
+  const uint8_t* sa[4];
+  const uint8_t* sw[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    sa[i] = p.As + (int64_t)min(m0 + wm * 64 + i * 16 + fr, p.M - 1) * p.ldas;
+    sw[i] = p.Ws + (int64_t)min(n0 + wn * 64 + i * 16 + fr, p.N - 1) * p.ldws;
+  }
+
+  u32x4 ra[4], rw[4];
+  int xa[4], xw[4];
+  auto fetch = [&](int kt) {
+    const int k0 = kt * MX_BK;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int ch = (tid + 256 * q) & 7;
+      const bool in = k0 + ch * 16 < p.K;
+      ra[q] = in ? ld_global16(ga[q] + k0) : u32x4{0u, 0u, 0u, 0u};
+      rw[q] = in ? ld_global16(gw[q] + k0) : u32x4{0u, 0u, 0u, 0u};
+    }
+    const int kb = kt * 4 + fq;  // past K (zero-filled half step): any finite scale, 2^0
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      xa[i] = kb < kblocks ? (int)sa[i][kb] : 127;
+      xw[i] = kb < kblocks ? (int)sw[i][kb] : 127;
+    }
+  };
+  auto stage = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      *reinterpret_cast<u32x4*>(&lds[buf][0][lo[q]]) = ra[q];
+      *reinterpret_cast<u32x4*>(&lds[buf][1][lo[q]]) = rw[q];
+    }
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    int ca[4], cw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      ca[i] = xa[i];
+      cw[i] = xw[i];
+    }
+    if (kt + 1 < nk) fetch(kt + 1);
+    i32x8 fa[4], fw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int ra_ = wm * 64 + i * 16 + fr, rw_ = wn * 64 + i * 16 + fr;
+      const u32x4 a0 = *reinterpret_cast<const u32x4*>(&lds[buf][0][swz(ra_, fq)]);
+      const u32x4 a1 = *reinterpret_cast<const u32x4*>(&lds[buf][0][swz(ra_, 4 + fq)]);
+      const u32x4 w0 = *reinterpret_cast<const u32x4*>(&lds[buf][1][swz(rw_, fq)]);
+      const u32x4 w1 = *reinterpret_cast<const u32x4*>(&lds[buf][1][swz(rw_, 4 + fq)]);
+      fa[i] = i32x8{(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+      fw[i] = i32x8{(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3], (int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[j], fa[i], acc[i][j], 0, 0, 0, cw[j], 0, ca[i]);
+    if (kt + 1 < nk) stage(buf ^ 1);
+    __syncthreads();
+  }
+
+  // ---- epilogue: bias (or column scale) -> GEGLU -> residual -> store, from the registers --------------------------------
+  const int nw0 = n0 + wn * 64;
+  if (nw0 >= p.N) return;  // (ragged last column tile: this wave's piece lies outside)
+  float bv[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int n = nw0 + j * 16 + 4 * fq;
+    const bool ok = p.bias != nullptr && n < p.N;
+    const f32x4 t = ok ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[j][r] = ok ? t[r] : (p.bias_mul ? 1.f : 0.f);
+  }
+  if constexpr (EPI == MX_EPI_GEGLU || EPI == MX_EPI_GEGLU_MX) {
+    // value block 2jj, gate block 2jj + 1 (weights packed [16 value | 16 gate]); the wave's 32 output columns are ONE MX block
+    const int nc = (nw0 >> 1) + 4 * fq;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + fr;
+      float v[8];
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          v[4 * jj + r] = (acc[i][2 * jj][r] + bv[2 * jj][r]) * gelu_erf_f(acc[i][2 * jj + 1][r] + bv[2 * jj + 1][r]);
+      if constexpr (EPI == MX_EPI_GEGLU_MX) {
+        uint32_t w0, w1;
+        const uint32_t code = mx8_block<16, 32>(v, w0, w1);  // (wave-wide shuffles: before the row mask)
+        if (m < p.M) {
+          uint8_t* cr = reinterpret_cast<uint8_t*>(p.C) + (int64_t)m * p.ldc + nc;
+          *reinterpret_cast<uint32_t*>(cr) = w0;
+          *reinterpret_cast<uint32_t*>(cr + 16) = w1;
+          if (fq == 0) p.Cs[(int64_t)m * p.ldcs + (nw0 >> 6)] = (uint8_t)code;
+        }
+      } else if (m < p.M) {
+        T* cr = reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + nc;
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          Pack4<T> o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o.e[r] = from_f32<T>(v[4 * jj + r]);
+          *reinterpret_cast<u32x2*>(cr + 16 * jj) = o.u;
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm * 64 + i * 16 + fr;
+      if (m >= p.M) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int n = nw0 + j * 16 + 4 * fq;
+        if (n >= p.N) continue;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = p.bias_mul ? acc[i][j][r] * bv[j][r] : acc[i][j][r] + bv[j][r];
+        if (p.R != nullptr) {
+          if (p.res32) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.R) + (int64_t)m * p.ldr + n);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] += t[r];
+          } else {
+            Pack4<T> t;
+            t.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.R) + (int64_t)m * p.ldr + n);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] += to_f32(t.e[r]);
+          }
+        }
+        if constexpr (EPI == MX_EPI_F32) {
+          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n) = f32x4{v[0], v[1], v[2], v[3]};
+        } else {
+          Pack4<T> o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o.e[r] = from_f32<T>(v[r]);
+          *reinterpret_cast<u32x2*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) = o.u;
+        }
+      }
+    }
+  }
+}
+
+inline bool aligned(const void* ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
+
+}  // namespace
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" int pm_quant_mx8(const void* x, int64_t ldx, const float* gamma, const float* beta, float eps, void* q, int64_t ldq,
+                            void* scales, int64_t lds, int64_t M, int64_t K, int in_dtype, void* stream) {
+  if (!x || !q || !scales || ((gamma == nullptr) != (beta == nullptr))) return PM_E_NULL;
+  const bool ln = gamma != nullptr;
+  if (in_dtype != PM_F16 && in_dtype != PM_BF16 && in_dtype != PM_F32) return PM_E_DTYPE;
+  const int64_t amask = in_dtype == PM_F32 ? 3 : 7;
+  if (M < 1 || K < 32 || (K & 31) || K > (1 << 24) || ldx < K || (ldx & amask) || ldq < K || (ldq & 7) || lds < K / 32 ||
+      !aligned(x, 16) || !aligned(q, 8) || M > (int64_t)1 << 30)
+    return PM_E_SHAPE;
+  if (ln && (in_dtype != PM_F32 || K > QMAX_IT * 512 || !aligned(gamma, 16) || !aligned(beta, 16))) return PM_E_SHAPE;
+  const dim3 grid((unsigned)((M + 3) / 4));
+  const hipStream_t st = (hipStream_t)stream;
+  uint8_t* qo = static_cast<uint8_t*>(q);
+  uint8_t* so = static_cast<uint8_t*>(scales);
+  if (ln) {
+    hipLaunchKernelGGL((mx8_quant_kernel<float, true>), grid, dim3(256), 0, st, (const float*)x, ldx, gamma, beta, eps, qo, ldq,
+                       so, lds, (int)M, (int)K);
+  } else if (in_dtype == PM_F32) {
+    hipLaunchKernelGGL((mx8_quant_kernel<float, false>), grid, dim3(256), 0, st, (const float*)x, ldx, nullptr, nullptr, 0.f,
+                       qo, ldq, so, lds, (int)M, (int)K);
+  } else if (in_dtype == PM_F16) {
+    hipLaunchKernelGGL((mx8_quant_kernel<f16, false>), grid, dim3(256), 0, st, (const f16*)x, ldx, nullptr, nullptr, 0.f, qo,
+                       ldq, so, lds, (int)M, (int)K);
+  } else {
+    hipLaunchKernelGGL((mx8_quant_kernel<bf16, false>), grid, dim3(256), 0, st, (const bf16*)x, ldx, nullptr, nullptr, 0.f, qo,
+                       ldq, so, lds, (int)M, (int)K);
+  }
+  return check_launch();
+}
+
+extern "C" int pm_gemm_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, int64_t ldw, const void* Ws,
+                           int64_t ldws, const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, void* Cs,
+                           int64_t ldcs, int64_t M, int64_t N, int64_t K, int act, int flags, int dtype, void* stream) {
+  if (!Aq || !As || !Wq || !Ws || !C) return PM_E_NULL;
+  const bool mx_out = (dtype & PM_OUT_MX8) != 0;
+  const int dt = dtype & ~PM_OUT_MX8;
+  if (dt & ~0xff) return PM_E_SHAPE;  // (PM_OUT_HILO and any other output mode)
+  if (dt != PM_F16 && dt != PM_BF16) return PM_E_DTYPE;
+  const int known = PM_FLAG_OUT_F32 | PM_FLAG_RES_F32 | PM_FLAG_BIAS_IS_SCALE;
+  if (flags & ~known) return PM_E_SHAPE;  // A_F32, A_LO, W_WRAP, STATS_I64 (and its instance count) are not served
+  const bool out32 = flags & PM_FLAG_OUT_F32, res32 = flags & PM_FLAG_RES_F32, bmul = flags & PM_FLAG_BIAS_IS_SCALE;
+  const bool geglu = act == PM_ACT_GEGLU;
+  if (act != PM_ACT_NONE && !geglu) return PM_E_SHAPE;
+  if (M < 1 || M > (int64_t)1 << 30 || N < 32 || (N & 31) || N > (1 << 24) || K < 64 || (K & 63) || K > (1 << 24))
+    return PM_E_SHAPE;
+  if (lda < K || ldw < K || (lda & 15) || (ldw & 15) || ldas < K / 32 || ldws < K / 32 || !aligned(Aq, 16) || !aligned(Wq, 16))
+    return PM_E_SHAPE;
+  if (bmul && (bias == nullptr || geglu)) return PM_E_SHAPE;
+  if (mx_out && (!geglu || Cs == nullptr)) return mx_out && Cs == nullptr ? PM_E_NULL : PM_E_SHAPE;
+  if (geglu && ((N & 63) || out32 || res32 || residual != nullptr)) return PM_E_SHAPE;
+  if (out32 && res32) return PM_E_SHAPE;
+  if (res32 && residual == nullptr) return PM_E_SHAPE;
+  const int64_t nout = geglu ? N / 2 : N;
+  if (ldc < nout || (ldc & 3) || (bias != nullptr && !aligned(bias, 16))) return PM_E_SHAPE;
+  if (mx_out && (ldcs < nout / 32 || !aligned(C, 4))) return PM_E_SHAPE;
+  if (!mx_out && !aligned(C, out32 ? 16 : 8)) return PM_E_SHAPE;
+  if (residual != nullptr && (ldr < N || (ldr & 3) || !aligned(residual, (out32 || res32) ? 16 : 8))) return PM_E_SHAPE;
+  Mx8Params p;
+  p.A = static_cast<const uint8_t*>(Aq);
+  p.lda = lda;
+  p.As = static_cast<const uint8_t*>(As);
+  p.ldas = ldas;
+  p.W = static_cast<const uint8_t*>(Wq);
+  p.ldw = ldw;
+  p.Ws = static_cast<const uint8_t*>(Ws);
+  p.ldws = ldws;
+  p.bias = bias;
+  p.R = residual;
+  p.ldr = ldr;
+  p.C = C;
+  p.ldc = ldc;
+  p.Cs = static_cast<uint8_t*>(Cs);
+  p.ldcs = ldcs;
+  p.M = (int)M;
+  p.N = (int)N;
+  p.K = (int)K;
+  p.bias_mul = bmul;
+  p.res32 = out32 || res32;
+  p.mtiles = (int)((M + MX_BM - 1) / MX_BM);
+  p.ntiles = (int)((N + MX_BN - 1) / MX_BN);
+  if ((int64_t)p.mtiles * p.ntiles > 0x7fffffff) return PM_E_SHAPE;
+  const dim3 grid((unsigned)(p.mtiles * p.ntiles));
+  const hipStream_t st = (hipStream_t)stream;
+  PM_DISPATCH_DTYPE(dt, T, {
+    if (mx_out)
+      hipLaunchKernelGGL((gemm_mx8_kernel<T, MX_EPI_GEGLU_MX>), grid, dim3(256), 0, st, p);
+    else if (geglu)
+      hipLaunchKernelGGL((gemm_mx8_kernel<T, MX_EPI_GEGLU>), grid, dim3(256), 0, st, p);
+    else if (out32)
+      hipLaunchKernelGGL((gemm_mx8_kernel<T, MX_EPI_F32>), grid, dim3(256), 0, st, p);
+    else
+      hipLaunchKernelGGL((gemm_mx8_kernel<T, MX_EPI_16>), grid, dim3(256), 0, st, p);
+  });
+  return check_launch();
+}

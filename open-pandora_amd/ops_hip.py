@@ -42,7 +42,7 @@ class HipOps:
     q_prescale = 64 ** -0.5 * 1.4426950408889634
 
     def __init__(self, dtype=torch.bfloat16, device="cuda", workspace_mb=256, fp8_attention=False, fp8_min_tokens=2048,
-                 parity=False, diag=False):
+                 parity=False, diag=False, fp8_linear=False, fp8_linear_min_rows=8192):
         if dtype not in _DT:
             raise ValueError(f"HipOps supports float16/bfloat16 activations, got {dtype}")
         # diag=True: this op table runs on the -DPM_DIAG build of the library (kernel-variant overrides, tuning
@@ -51,6 +51,13 @@ class HipOps:
         # BASELINE configs[4]: the spatial self-attention of the U-Net on pm_attention_fp8 (opt-in: ~2-3e-2 per call)
         self.fp8_attention = bool(fp8_attention)
         self.fp8_min_tokens = int(fp8_min_tokens)  # shorter sequences stay on pm_attention (the packing pass costs more than it saves)
+        # MXFP8 projections of the transformer blocks (pm_quant_mx8 / pm_gemm_mx8: e4m3 with one power-of-two scale per 32 values
+        # along K, opt-in): UNetModel.prepare quantises the six block weights once and UNetModel._block routes every site with at
+        # least `fp8_linear_min_rows` rows through them; smaller sites stay on the 16-bit kernels
+        self.fp8_linear = bool(fp8_linear)
+        self.fp8_linear_min_rows = int(fp8_linear_min_rows)
+        if self.fp8_linear and parity:
+            raise ValueError("fp8_linear=True and parity: one is a reduced-precision mode, the other carries extra mantissa")
         if os.environ.get("PANDORA_Q_PRESCALE", "1") == "0":  # (numerics experiments: scale inside the kernel)
             self.q_prescale = None
         # LayerNorm + projection pairs of the shallow levels as ONE kernel (pm_ln_gemm); "0": the two-kernel pair (A/B)
@@ -488,6 +495,59 @@ class HipOps:
             capi.check(rc, f"pm_ln_gemm M={M} N={N} K={K}")
             return out
         return self.gemm(self.layernorm(x, gamma, beta, eps), w, bias, act=act, col_scale=col_scale)
+
+    # -- MXFP8 projections (fp8_linear) -------------------------------------------------------------
+    def _mx8_pair(self, M, K):
+        return (torch.empty(M, K, dtype=torch.uint8, device=self.device),
+                torch.empty(M, K // 32, dtype=torch.uint8, device=self.device))
+
+    def quant_mx8(self, x):
+        """x [M, K] (16-bit or f32, last dim contiguous) -> (e4m3 [M, K] uint8, E8M0 scales [M, K/32] uint8): pm_quant_mx8."""
+        M, K = x.shape
+        assert x.stride(1) == 1 and x.dtype in (torch.float16, torch.bfloat16, torch.float32), (x.dtype, x.stride())
+        q, s = self._mx8_pair(M, K)
+        dt = _F32 if x.dtype == torch.float32 else _DT[x.dtype]
+        rc = self.lib.pm_quant_mx8(_ptr(x), x.stride(0), None, None, 0.0, _ptr(q), q.stride(0), _ptr(s), s.stride(0), M, K, dt,
+                                   self._stream())
+        capi.check(rc, f"pm_quant_mx8 M={M} K={K}")
+        return q, s
+
+    def ln_quant_mx8(self, x, gamma, beta, eps=1e-5):
+        """LayerNorm of the f32 stream x [M, K] quantised to MXFP8 in one pass (pm_quant_mx8, LayerNorm mode)."""
+        M, K = x.shape
+        assert x.dtype == torch.float32 and x.stride(1) == 1
+        q, s = self._mx8_pair(M, K)
+        rc = self.lib.pm_quant_mx8(_ptr(x), x.stride(0), _ptr(gamma), _ptr(beta), float(eps), _ptr(q), q.stride(0), _ptr(s),
+                                   s.stride(0), M, K, _F32, self._stream())
+        capi.check(rc, f"pm_quant_mx8 (LayerNorm) M={M} K={K}")
+        return q, s
+
+    def gemm_mx8(self, a, w, bias=None, residual=None, act="none", out=None, stream=False, col_scale=None, mx_out=False):
+        """out = epi(deq(a) @ deq(w)^T) for MXFP8 pairs a = (e4m3 [M, K], scales [M, K/32]), w = (e4m3 [N, K], scales) (pm_gemm_mx8).
+        Flavours as gemm(): bias / col_scale, stream=True (f32 output onto the f32 residual), an f32 residual with 16-bit output,
+        act="geglu" (N/2 output columns) and, with mx_out=True, GEGLU straight to an MXFP8 pair (the A operand of the next GEMM)."""
+        (aq, as_), (wq, ws) = a, w
+        M, K = aq.shape
+        N = wq.shape[0]
+        assert wq.shape[1] == K and as_.shape == (M, K // 32) and ws.shape == (N, K // 32) and aq.stride(1) == 1
+        n_out = N // 2 if act == "geglu" else N
+        dt = self.dt
+        cs = None
+        if mx_out:
+            assert act == "geglu" and residual is None and not stream
+            out, cs = self._mx8_pair(M, n_out)
+            flags, dt = 0, dt | capi.PM_OUT_MX8
+        else:
+            flags, out = self._gemm_io(aq, residual, out, M, n_out, stream)
+        if col_scale is not None:
+            assert bias is None and col_scale.dtype == torch.float32 and col_scale.numel() == N
+            bias, flags = col_scale, flags | capi.PM_FLAG_BIAS_IS_SCALE
+        rc = self.lib.pm_gemm_mx8(_ptr(aq), aq.stride(0), _ptr(as_), as_.stride(0), _ptr(wq), wq.stride(0), _ptr(ws), ws.stride(0),
+                                  _ptr(bias), _ptr(residual), residual.stride(0) if residual is not None else 0, _ptr(out),
+                                  out.stride(0), _ptr(cs), cs.stride(0) if cs is not None else 0, M, N, K, capi.ACT_CODES[act],
+                                  flags, dt, self._stream())
+        capi.check(rc, f"pm_gemm_mx8 M={M} N={N} K={K}")
+        return (out, cs) if mx_out else out
 
     def attention(self, q, k1, v1, heads, k2=None, v2=None, w2=1.0, out=None, prescaled=False):
         """q [B, Nq, heads*64] view; kX/vX [B or 1, NkX, heads*64] views (last dim contiguous).

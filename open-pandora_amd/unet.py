@@ -375,6 +375,12 @@ class UNetModel(packing.PackedWeights, nn.Module):
                 gw, gb = packing.pack_geglu(blk.ff.net[0].proj.weight.detach(), blk.ff.net[0].proj.bias.detach())
                 e["ff1"] = (wt(gw), f32(gb))
                 e["ff2"] = lin(blk.ff.net[2])
+                if getattr(ops, "fp8_linear", False):
+                    # MXFP8 mode: the six projections of the block quantised ONCE, after the packing above (the q|k|v
+                    # concatenation and the GEGLU interleave carry over), by the same kernel and rule as the activations
+                    mx = {k: ops.quant_mx8(e[k]) for k in ("a1_qkv", "a2_qkv", "a2_q") if k in e}
+                    mx.update({k: ops.quant_mx8(e[k][0]) for k in ("a1_out", "a2_out", "ff1", "ff2")})
+                    e["mx8"] = mx
                 W[name] = e
             elif isinstance(mod, Downsample):
                 W[name] = (wt(packing.pack_conv3x3(mod.op.weight)), f32(mod.op.bias))
@@ -522,13 +528,19 @@ class UNetModel(packing.PackedWeights, nn.Module):
         ops = c.ops
         inner, heads = mod.inner, mod.heads
         v3 = lambda t, n: t.view(F, P, n)
+        # MXFP8 mode (HipOps(fp8_linear=True)): the six projections of a block with enough rows run on pm_gemm_mx8, their A
+        # operands quantised by pm_quant_mx8 (LayerNorm-fused for the three LayerNorm sites); everything else stays as it is
+        mx = e.get("mx8") if getattr(ops, "fp8_linear", False) and h.shape[0] >= ops.fp8_linear_min_rows else None
         for which in (1, 2):
             ln = e[f"ln{which}"]  # (LayerNorm and the projection behind it are one op: ops.ln_gemm)
             key = f"a{which}_qkv"
             if key in e:  # self-attention, fused q|k|v projection
                 qs = e.get("a1_qscale") if which == 1 else None
                 self._site(c, f"ln{'t' if temporal else 's'}{which}")
-                qkv = v3(ops.ln_gemm(h, *ln, e[key], col_scale=qs), 3 * inner)
+                if mx is not None:
+                    qkv = v3(ops.gemm_mx8(ops.ln_quant_mx8(h, *ln), mx[key], col_scale=qs), 3 * inner)
+                else:
+                    qkv = v3(ops.ln_gemm(h, *ln, e[key], col_scale=qs), 3 * inner)
                 q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
                 if temporal:
                     if gather:  # frame-sharded without the pixel re-shard: all-gather K|V over frames
@@ -548,7 +560,10 @@ class UNetModel(packing.PackedWeights, nn.Module):
                     a = ops.attention(q, k, v, heads)
             else:  # spatial cross-attention: text keys shared by all frames + per-frame image keys
                 self._site(c, "lns2")
-                q = v3(ops.ln_gemm(h, *ln, e["a2_q"]), inner)
+                if mx is not None:
+                    q = v3(ops.gemm_mx8(ops.ln_quant_mx8(h, *ln), mx["a2_q"]), inner)
+                else:
+                    q = v3(ops.ln_gemm(h, *ln, e["a2_q"]), inner)
                 lo, hi = e["a2_kv_slice"]
                 kv_t = c.kv_text[:, lo:hi].unflatten(0, (c.B, -1))  # [B, 77, 2*inner] view of the batched projection
                 kv_i = None
@@ -567,8 +582,15 @@ class UNetModel(packing.PackedWeights, nn.Module):
                     got = ops.attention(q[sl], kv_t[j:j + 1, :, :inner], kv_t[j:j + 1, :, inner:], heads, k2, v2, e.get("a2_w2", 1.0),
                                         out=None if a is None else a[sl])
                     a = got if a is None else a
-            h = ops.gemm(a.view(F * P, inner), *e[f"a{which}_out"], residual=h, stream=True)
+            if mx is not None:
+                h = ops.gemm_mx8(ops.quant_mx8(a.view(F * P, inner)), mx[f"a{which}_out"], e[f"a{which}_out"][1], residual=h,
+                                 stream=True)
+            else:
+                h = ops.gemm(a.view(F * P, inner), *e[f"a{which}_out"], residual=h, stream=True)
         self._site(c, f"ln{'t' if temporal else 's'}3")
+        if mx is not None:  # GEGLU straight to MXFP8: ff2's A operand needs no quantisation pass of its own
+            g = ops.gemm_mx8(ops.ln_quant_mx8(h, *e["ln3"]), mx["ff1"], e["ff1"][1], act="geglu", mx_out=True)
+            return ops.gemm_mx8(g, mx["ff2"], e["ff2"][1], residual=h)
         g = ops.ln_gemm(h, *e["ln3"], e["ff1"][0], e["ff1"][1], act="geglu")
         # the block's last add: its only consumer is proj_out's A operand (16-bit anyway), so the sum
         # (formed in f32 against the f32 stream) is stored as 16 bit
