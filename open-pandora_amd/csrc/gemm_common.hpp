@@ -63,6 +63,30 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + (bid >> 3);
 }
 
+// work item -> (row tile, column tile, K slice) for the 2-stage and the ring kernels.  Supertile order: workgroups that
+// run together on one XCD (a contiguous run of ids) cover GM row tiles x several column tiles, so both the A and the W
+// panels they stream stay in that XCD's 4 MiB L2 (row-major order re-fetched the whole W panel set
+// for every row tile: 9x the algorithmic bytes on the wide GEGLU GEMM, profiles/r01/pmc_traffic.md)
+template <int AMODE, int TILE_ROWS>
+__device__ __forceinline__ void decode_work(const GemmParams& p, int w, int& mt, int& nt, int& split) {
+  constexpr int GM = 8;
+  split = w % p.splits;
+  const int wg = w / p.splits;
+  const int grp = wg / (GM * p.ntiles);
+  const int first_m = grp * GM;
+  const int gm = (p.mtiles - first_m < GM) ? p.mtiles - first_m : GM;
+  const int rin = wg - grp * GM * p.ntiles;
+  nt = rin / gm;
+  mt = first_m + (rin - nt * gm);
+  if (AMODE == A_CONVT3) {
+    // temporal conv: row tile (frame f, pixel block b) reads the same pixel block of frames f-1, f, f+1.
+    // Enumerate the row tiles pixel-block-major (consecutive ids = consecutive frames of one block), so the
+    // three readers of an input tile run together on one XCD instead of a whole frame of tiles apart
+    const int bpf = p.P / TILE_ROWS;  // pixel blocks per frame (remap only when tiles do not straddle frames)
+    if (bpf * TILE_ROWS == p.P && p.mtiles == bpf * p.F) mt = (mt % p.F) * bpf + (mt / p.F);
+  }
+}
+
 // ---- GroupNorm totals by deterministic integer atomics (r06, VERDICT r05 #3a/b) -------------------------------------------------
 // The fused statistics used to leave per-(row block, column) sums behind and every consumer GroupNorm paid a finalize launch
 // (156-165 gn_finalize_colstats + 20-35 gn_finalize of ~1050 launches per forward).  A float atomic would make the totals depend

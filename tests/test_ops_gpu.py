@@ -365,7 +365,7 @@ def test_gemm_wide_stream_one_statement_kernel(hip_ops_factory, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_gemm_ringw_256x128_tiles(hip_ops_factory, dtype):
-    """gemm_ringw_kernel (the ring kernel on 256x128 tiles, csrc/gemm.hip), selected by the library's own rule
+    """gemm_ringw_kernel (the ring kernel on 256x128 tiles, csrc/gemm_ring.hpp), selected by the library's own rule
     (pm_gemm_kernel_choice == 3: unsplit, K >= 512, whole rounds of 256-row tiles): exact-integer product with a ragged last
     row tile, bias / GEGLU, f32 residual + fused GroupNorm statistics, and the temporal-conv loader incl. halo frames."""
     ops = hip_ops_factory(dtype)
