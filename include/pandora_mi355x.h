@@ -274,6 +274,29 @@ int pm_attention_fp8(const void* q, int64_t q_bs, int64_t q_rs, const void* k, c
                      int64_t Nq, float scale, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Packed fp8 attention operands: what pm_attention_fp8 builds in its workspace, as a public layout, so that a producer can
+ * write it directly (pm_gemm_mx8_qkv_fp8 below) and the attention kernel can be called without a packing pass.
+ *   q8  [B*heads][Nq_pad][64]  e4m3 rows of q' = q * scale * log2(e) (scores in the base-2 domain);
+ *   k8  [B*heads][Nk_pad][64]  e4m3 rows of k;
+ *   v8t [B*heads][64][Nk_pad]  e4m3 v, transposed per (batch item, head); inside each tile of 64 keys, key r = 8 g + 4 h + e
+ *                              (g = 0..7, h = 0..1, e = 0..3) sits at byte 32 h + 4 g + e of the tile's 64-byte row, i.e.
+ *                              pos(r) = 32 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3) - the order in which a lane of the
+ *                              attention kernel holds the probabilities of a tile (its P^T operand).
+ *   N*_pad = N rounded up to a multiple of 64; the padding rows (q8, k8) / key bytes (v8t) are zero.  16-byte aligned bases.
+ * Elements are e4m3fn codes of the value clamped to +-448; NaN -> 0x7F.
+ *
+ * pm_attention_fp8_packed: the attention kernel of pm_attention_fp8 alone, on packed operands.  pm_attention_fp8 is exactly its
+ * packing pass followed by this call.  o as pm_attention (o_bs / o_rs in elements, multiples of 8), `dtype` PM_F16 / PM_BF16.
+ * With PM_OUT_MX8 OR-ed into `dtype`, O leaves as MXFP8 (section "MXFP8" below): e4m3 bytes o [B, Nq, heads*64] (o_bs / o_rs in
+ * bytes, multiples of 4, o 4-byte aligned) plus E8M0 scales os [B, Nq, heads*2] (os_bs / os_rs in bytes), one block per 32
+ * channels, quantised by the MXFP8 rule from the f32 output (after the 1/l normalisation; no 16-bit rounding in between) - the A
+ * operand of to_out (attention.py:144) without a pm_quant_mx8 pass.  os is ignored (may be NULL) otherwise.
+ */
+int pm_attention_fp8_packed(const void* q8, const void* k8, const void* v8t, int64_t Nq, int64_t Nk, void* o, int64_t o_bs,
+                            int64_t o_rs, void* os, int64_t os_bs, int64_t os_rs, int64_t B, int64_t heads, int dtype,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * pm_attention_generic: softmax(q k^T * scale) v for ANY head dim D <= 128 (D % 8 == 0) and Nk <= 1024, f32
  * arithmetic, single key/value segment.  For the OpenCLIP ViT-H/14 image tower of the conditioning tail
  * (nn.MultiheadAttention with 16 heads of 80 channels over 257 tokens, condition.py:300-382, once per generate call);
@@ -296,7 +319,8 @@ int pm_attention_generic(const void* q, int64_t q_bs, int64_t q_rs, const void* 
  *     is NaN.
  * The same rule quantises weights (UNetModel.prepare, once) and activations (per call); tests/test_mx8_cpu.py restates it.
  */
-#define PM_OUT_MX8 0x400 /* OR-ed into the `dtype` of pm_gemm_mx8: C is MXFP8 (e4m3 [M, Nout] + E8M0 scales [M, Nout/32] in Cs) */
+#define PM_OUT_MX8 0x400 /* OR-ed into the `dtype` of pm_gemm_mx8: C is MXFP8 (e4m3 [M, Nout] + E8M0 scales [M, Nout/32] in Cs);
+                          * into the `dtype` of pm_attention_fp8_packed: O is MXFP8 */
 
 /* pm_quant_mx8: x [M, K] (in_dtype PM_F16 / PM_BF16 / PM_F32, row stride ldx) -> e4m3 q [M, K] (ldq) + scales [M, K/32] (lds).
  *   plain (gamma == beta == NULL): the attention output in front of to_out (attention.py:144).
@@ -325,6 +349,23 @@ int pm_quant_mx8(const void* x, int64_t ldx, const float* gamma, const float* be
 int pm_gemm_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, int64_t ldw, const void* Ws,
                 int64_t ldws, const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, void* Cs, int64_t ldcs,
                 int64_t M, int64_t N, int64_t K, int act, int flags, int dtype, void* stream);
+
+/* pm_gemm_mx8_qkv_fp8: the fused q|k|v projection of a spatial self-attention (to_q / to_k / to_v, attention.py:86-99, feeding
+ * the attention of :101-125) in MXFP8, writing the packed fp8 attention operands (layout above, Nq = Nk = P) instead of a 16-bit
+ * [M, 3*inner] matrix: no q|k|v round trip through memory and no packing pass.
+ *   Aq / As / Wq / Ws as pm_gemm_mx8: A = MXFP8 of LayerNorm(x) [M, K], W = MXFP8 [3*heads*64, K] (q rows, then k, then v).
+ *   M = B * P rows: row m is token m % P of batch item m / P; column n is part n / inner (0 q, 1 k, 2 v), head
+ *   (n % inner) / 64, channel n % 64, inner = heads * 64.
+ *   element: y = acc * bias[n] with PM_FLAG_BIAS_IS_SCALE (the only flag accepted; how the softmax prescale of the q third
+ *   arrives), else acc + bias[n] (bias may be NULL); q columns then * qmul (pass 1 when the prescale is in the column scale,
+ *   scale * log2(e) otherwise); clamp to +-448; e4m3 by round-to-nearest-even in software (subnormals included, as the MXFP8
+ *   rule rounds elements); NaN -> 0x7F.  The arithmetic up to the rounding is that of pm_gemm_mx8 with PM_FLAG_OUT_F32.
+ *   Served: P % 64 == 0 (P >= 64), M % P == 0, K % 64 == 0; 16-byte aligned q8 / k8 / v8t of B*heads*P*64 bytes each.  Everything
+ *   else returns PM_E_SHAPE (callers then run pm_gemm_mx8 + pm_attention_fp8).
+ */
+int pm_gemm_mx8_qkv_fp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, int64_t ldw, const void* Ws,
+                        int64_t ldws, const float* bias, void* q8, void* k8, void* v8t, int64_t M, int64_t K, int64_t heads,
+                        int64_t P, float qmul, int flags, void* stream);
 
 /* (Diagnostics - kernel-variant overrides, ceiling probes, environment tuning switches - are NOT part of this library:
  * they exist only in the -DPM_DIAG build, libpandora_mi355x_diag.so, declared in include/pandora_mi355x_diag.h.  This

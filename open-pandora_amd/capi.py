@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PANDORA_LIB", DIAG_LIB_PATH if os.environ.get("PANDOR
 
 PM_F16, PM_BF16, PM_F32 = 1, 2, 3
 PM_OUT_HILO = 0x100
-PM_OUT_MX8 = 0x400  # pm_gemm_mx8 `dtype`: MXFP8 output (GEGLU)
+PM_OUT_MX8 = 0x400  # pm_gemm_mx8 `dtype`: MXFP8 output (GEGLU); pm_attention_fp8_packed `dtype`: MXFP8 O
 PM_TOTALS_I64, PM_FLAG_STATS_I64 = 0x200, 64
 PM_FLAG_A_F32, PM_FLAG_OUT_F32, PM_FLAG_RES_F32, PM_FLAG_BIAS_IS_SCALE, PM_FLAG_A_LO, PM_FLAG_W_WRAP = 1, 2, 4, 8, 16, 32
 PM_ACT_NONE, PM_ACT_SILU, PM_ACT_GEGLU, PM_ACT_GELU = 0, 1, 2, 3
@@ -63,6 +63,8 @@ SIGNATURES = {
     "pm_attention_fp8": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                  c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p, c_size_t,
                                  c_void_p]),
+    "pm_attention_fp8_packed": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+                                        c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "pm_attention_generic": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                      c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p]),
     "pm_attention_temporal": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
@@ -86,6 +88,8 @@ SIGNATURES = {
     "pm_gemm_mx8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                             c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
                             c_void_p]),
+    "pm_gemm_mx8_qkv_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p]),
     "pm_peer_mailbox_bytes": (c_size_t, [c_int, c_int64, c_int64]),
     "pm_peer_create": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p]),
     "pm_peer_open": (c_int, [c_void_p, c_void_p]),

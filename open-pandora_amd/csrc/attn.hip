@@ -11,6 +11,7 @@
 //                      come from the row-major V tile through ds_read_b64_tr_b16.
 // Two key/value segments (text, image) are normalised independently and summed (attention.py:128-142).
 #include "attn_common.hpp"
+#include "mx8_common.hpp"
 
 namespace pm {
 
@@ -619,6 +620,9 @@ struct AttnFp8Params {
   void* o;
   int64_t o_bs, o_rs;
   int Nq, Nk, Nq_pad, Nk_pad, heads, nqt;
+  // MXFP8 output (MXO) only: o is e4m3 [B, Nq, heads * 64] (o_bs / o_rs in bytes), os its E8M0 scales [B, Nq, heads * 2]
+  unsigned char* os;
+  int64_t os_bs, os_rs;
 };
 
 constexpr int F8_TILE_BYTES = 64 * 64;  // one K or V^T tile
@@ -628,7 +632,7 @@ __device__ __forceinline__ f32x16 mfma_f8(i32x8 a, i32x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);  // fp8 x fp8, scales 2^0
 }
 
-template <typename T, int QB>
+template <typename T, int QB, bool MXO = false>
 __global__ __launch_bounds__(256, 2) void attn_fp8_kernel(const AttnFp8Params p) {
   constexpr int RING = 2;
   __shared__ __attribute__((aligned(16))) char smem[2 * RING * F8_TILE_BYTES];
@@ -808,7 +812,41 @@ __global__ __launch_bounds__(256, 2) void attn_fp8_kernel(const AttnFp8Params p)
   for (int qb = 0; qb < QB; ++qb) {
     const float l_tot = l_run[qb] + other_half(l_run[qb]);
     const float inv = 1.0f / l_tot;
-    if (q_valid[qb]) {
+    if constexpr (MXO) {
+      // O as MXFP8, quantised from the f32 value: channels 32 db .. + 31 of a head are one block, of which this lane holds 16
+      // (d = 32 db + 8 g + 4 hh + e) and lane ^ 32 the other 16 - the block maximum is one exchange
+      unsigned char* op = reinterpret_cast<unsigned char*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow[qb] * p.o_rs + head * 64;
+      unsigned char* sp = p.os + (int64_t)b * p.os_bs + (int64_t)qrow[qb] * p.os_rs + head * 2;
+#pragma unroll
+      for (int db = 0; db < 2; ++db) {
+        float v[16];
+        float amax = 0.f;
+        int bad = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          v[r] = oacc[qb][db][r] * inv;
+          amax = fmaxf(amax, fabsf(v[r]));
+          bad |= finite_f(v[r]) ? 0 : 1;
+        }
+        amax = fmaxf(amax, other_half(amax));
+        bad |= __shfl_xor(bad, 32, 64);
+        const int X = mx8_exp(amax);
+        const float sc = mx8_inv_scale(X);
+        if (q_valid[qb]) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            uint32_t w = 0x7f7f7f7fu;
+            if (!bad) {
+              w = 0;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) w |= e4m3_rne(v[4 * g + e] * sc) << (8 * e);
+            }
+            *reinterpret_cast<uint32_t*>(op + db * 32 + 8 * g + 4 * hh) = w;
+          }
+          if (hh == 0) sp[db] = bad ? (unsigned char)0xff : (unsigned char)(X + 127);
+        }
+      }
+    } else if (q_valid[qb]) {
       T* op = reinterpret_cast<T*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow[qb] * p.o_rs + head * 64;
 #pragma unroll
       for (int db = 0; db < 2; ++db)
@@ -1190,6 +1228,57 @@ extern "C" size_t pm_attention_fp8_workspace_bytes(int64_t B, int64_t heads, int
   return (size_t)(B * heads * 64 * (nq + 2 * nk));
 }
 
+// attn_fp8_kernel on packed operands (p.q8 / k8 / v8t / o / os and the sizes filled in); dtype may carry PM_OUT_MX8
+static int launch_attn_fp8(AttnFp8Params p, int64_t B, int dtype, hipStream_t stream) {
+#ifdef PM_DIAG
+  const bool qb2 = attn_variant() == 2 && !(dtype & PM_OUT_MX8);  // (32 rows per wave measured faster at every N: tools/attn_bench.py 101 / 102)
+#else
+  constexpr bool qb2 = false;
+#endif
+  const int rows = qb2 ? 256 : 128;
+  p.nqt = (int)((p.Nq + rows - 1) / rows);
+  dim3 grid((unsigned)(p.nqt * B * p.heads));
+  if (dtype & PM_OUT_MX8) {
+    hipLaunchKernelGGL((attn_fp8_kernel<f16, 1, true>), grid, dim3(256), 0, stream, p);  // (the element type is unused)
+    return check_launch();
+  }
+  PM_DISPATCH_DTYPE(dtype, T,
+                    if constexpr (PM_DIAG_BUILD) {
+                      if (qb2) {
+                        hipLaunchKernelGGL((attn_fp8_kernel<T, PM_DIAG_BUILD ? 2 : 1>), grid, dim3(256), 0, stream, p);
+                        return check_launch();
+                      }
+                    }
+                    hipLaunchKernelGGL((attn_fp8_kernel<T, 1>), grid, dim3(256), 0, stream, p);
+                    return check_launch());
+}
+
+extern "C" int pm_attention_fp8_packed(const void* q8, const void* k8, const void* v8t, int64_t Nq, int64_t Nk, void* o,
+                                       int64_t o_bs, int64_t o_rs, void* os, int64_t os_bs, int64_t os_rs, int64_t B,
+                                       int64_t heads, int dtype, void* stream) {
+  if (!q8 || !k8 || !v8t || !o) return PM_E_NULL;
+  const bool mx_out = (dtype & PM_OUT_MX8) != 0;
+  const int dt = dtype & ~PM_OUT_MX8;
+  if (dt & ~0xff) return PM_E_SHAPE;
+  if (dt != PM_F16 && dt != PM_BF16) return PM_E_DTYPE;
+  if (mx_out && !os) return PM_E_NULL;
+  if (B < 1 || heads < 1 || Nq < 1 || Nk < 1) return PM_E_SHAPE;
+  if (mx_out ? (((o_bs | o_rs) & 3) || o_rs < heads * 64 || os_rs < heads * 2 || (reinterpret_cast<uintptr_t>(o) & 3))
+             : (((o_bs | o_rs) & 7) != 0))
+    return PM_E_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(q8) | reinterpret_cast<uintptr_t>(k8) | reinterpret_cast<uintptr_t>(v8t)) & 15) return PM_E_SHAPE;
+  const int64_t nq = (Nq + 63) / 64 * 64, nk = (Nk + 63) / 64 * 64;
+  if (nk * 64 >= (1ll << 31) || nq * 64 >= (1ll << 31) || B * heads > 65535) return PM_E_SHAPE;
+  AttnFp8Params p{};
+  p.q8 = static_cast<const unsigned char*>(q8);
+  p.k8 = static_cast<const unsigned char*>(k8);
+  p.v8t = static_cast<const unsigned char*>(v8t);
+  p.o = o; p.o_bs = o_bs; p.o_rs = o_rs;
+  p.os = static_cast<unsigned char*>(os); p.os_bs = os_bs; p.os_rs = os_rs;
+  p.Nq = (int)Nq; p.Nk = (int)Nk; p.Nq_pad = (int)nq; p.Nk_pad = (int)nk; p.heads = (int)heads;
+  return launch_attn_fp8(p, B, dtype, (hipStream_t)stream);
+}
+
 extern "C" int pm_attention_fp8(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v,
                                 int64_t k_bs, int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs,
                                 int64_t B, int64_t heads, int64_t Nq, float scale, int dtype, void* workspace,
@@ -1200,6 +1289,7 @@ extern "C" int pm_attention_fp8(const void* q, int64_t q_bs, int64_t q_rs, const
   if (workspace_bytes < pm_attention_fp8_workspace_bytes(B, heads, Nq, Nk)) return PM_E_WORKSPACE;
   const int64_t nq = (Nq + 63) / 64 * 64, nk = (Nk + 63) / 64 * 64;
   if (nk * 64 >= (1ll << 31) || B * heads > 65535) return PM_E_SHAPE;
+  if (dtype != PM_F16 && dtype != PM_BF16) return PM_E_DTYPE;
   unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
   AttnFp8PackParams pp{};
   pp.q = q; pp.k = k; pp.v = v; pp.q_bs = q_bs; pp.q_rs = q_rs; pp.k_bs = k_bs; pp.k_rs = k_rs;
@@ -1211,24 +1301,10 @@ extern "C" int pm_attention_fp8(const void* q, int64_t q_bs, int64_t q_rs, const
   AttnFp8Params p{};
   p.q8 = pp.q8; p.k8 = pp.k8; p.v8t = pp.v8t; p.o = o; p.o_bs = o_bs; p.o_rs = o_rs;
   p.Nq = (int)Nq; p.Nk = (int)Nk; p.Nq_pad = (int)nq; p.Nk_pad = (int)nk; p.heads = (int)heads;
-#ifdef PM_DIAG
-  const bool qb2 = attn_variant() == 2;  // (32 rows per wave measured faster at every N: tools/attn_bench.py 101 / 102)
-#else
-  constexpr bool qb2 = false;
-#endif
-  const int rows = qb2 ? 256 : 128;
-  p.nqt = (int)((Nq + rows - 1) / rows);
-  dim3 grid((unsigned)(p.nqt * B * heads));
+  // pack + the packed-operand kernel (what pm_attention_fp8_packed launches)
   PM_DISPATCH_DTYPE(dtype, T,
-                    hipLaunchKernelGGL((attn_fp8_pack_kernel<T>), pgrid, dim3(256), 0, (hipStream_t)stream, pp);
-                    if constexpr (PM_DIAG_BUILD) {
-                      if (qb2) {
-                        hipLaunchKernelGGL((attn_fp8_kernel<T, PM_DIAG_BUILD ? 2 : 1>), grid, dim3(256), 0, (hipStream_t)stream, p);
-                        return check_launch();
-                      }
-                    }
-                    hipLaunchKernelGGL((attn_fp8_kernel<T, 1>), grid, dim3(256), 0, (hipStream_t)stream, p);
-                    return check_launch());
+                    hipLaunchKernelGGL((attn_fp8_pack_kernel<T>), pgrid, dim3(256), 0, (hipStream_t)stream, pp));
+  return launch_attn_fp8(p, B, dtype, (hipStream_t)stream);
 }
 
 extern "C" int pm_attention_generic(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v,

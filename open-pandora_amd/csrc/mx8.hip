@@ -3,38 +3,14 @@
 // block-scaled GEMM pm_gemm_mx8 on v_mfma_scale_f32_16x16x128_f8f6f4 (K = 128 per instruction at twice the bf16 rate, the
 // scales applied inside the instruction).  Quantisation rule: include/pandora_mi355x.h, "MXFP8".
 #include "gemm_common.hpp"
+#include "mx8_common.hpp"
 
 namespace pm {
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-// ---- the quantisation rule (restated in numpy by tests/test_mx8_cpu.py) --------------------------------------------------
-// Scale exponent of a block with amax a (finite): X = clamp(ceil(log2(a / 448)), -127, 127), exactly: a = 1.m * 2^e gives
-// X = e - 8 + (1.m > 1.75).  f32 subnormal a (and a = 0) give -127 (E8M0 code 0).
-__device__ __forceinline__ int mx8_exp(float amax) {
-  const uint32_t b = __float_as_uint(amax);
-  const int e = (int)((b >> 23) & 0xff);
-  if (e == 0) return -127;
-  const int X = e - 135 + ((b & 0x7fffff) > 0x600000u ? 1 : 0);
-  return X < -127 ? -127 : (X > 127 ? 127 : X);
-}
-// 2^-X as an f32 (X in [-127, 120] for finite inputs: always a normal number)
-__device__ __forceinline__ float mx8_inv_scale(int X) { return __uint_as_float((uint32_t)(127 - X) << 23); }
-// e4m3fn code of y (|y| <= 448, finite), round to nearest even, subnormals (steps of 2^-9) included.  In software so that the
-// result does not depend on the hardware converter's tie / subnormal handling.
-__device__ __forceinline__ uint32_t e4m3_rne(float y) {
-  uint32_t b = __float_as_uint(y);
-  const uint32_t s = (b >> 24) & 0x80u;
-  b &= 0x7fffffffu;
-  if (b >= 0x3c800000u) {  // |y| >= 2^-6: normal
-    b += 0x7ffffu + ((b >> 20) & 1u);
-    return s | (((b >> 23) - 120u) << 3) | ((b >> 20) & 7u);
-  }
-  return s | (uint32_t)__builtin_rintf(__uint_as_float(b) * 512.0f);  // 8 -> 0x08 = 2^-6, the smallest normal
-}
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e38f; }  // (false for NaN)
-
+// ---- the quantisation rule: mx8_exp / mx8_inv_scale / e4m3_rne of mx8_common.hpp -------------------------------------------
 // One block of 32 values spread over 4 lanes (8 each) that differ in lane-index bits O1 and O2: E8M0 code of the block and the
 // 8 e4m3 codes of this lane (two little-endian words).  A block holding a NaN or an Inf: code 0xFF and NaN (0x7F) elements.
 template <int O1, int O2>
@@ -179,7 +155,7 @@ __global__ __launch_bounds__(256) void mx8_quant_kernel(const TI* __restrict__ x
 constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 128;
 constexpr int MX_TILE = MX_BM * MX_BK;  // bytes per operand and buffer
 
-enum { MX_EPI_16 = 0, MX_EPI_F32 = 1, MX_EPI_GEGLU = 2, MX_EPI_GEGLU_MX = 3 };
+enum { MX_EPI_16 = 0, MX_EPI_F32 = 1, MX_EPI_GEGLU = 2, MX_EPI_GEGLU_MX = 3, MX_EPI_QKV8 = 4 };
 
 struct Mx8Params {
   const uint8_t* A;
@@ -201,6 +177,12 @@ struct Mx8Params {
   int bias_mul;  // PM_FLAG_BIAS_IS_SCALE
   int res32;     // residual is f32
   int mtiles, ntiles;
+  // MX_EPI_QKV8 only (appended: the other flavours' argument offsets stay where they were)
+  uint8_t* q8;
+  uint8_t* k8;
+  uint8_t* v8t;
+  int heads, P;  // tokens per batch item (P % 64 == 0, M = B * P)
+  float qmul;    // extra factor on the q columns (1 when the prescale arrives as the column scale)
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * MX_BK + ((chunk ^ (row & 7)) << 4); }
@@ -314,7 +296,75 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(Mx8Params p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) bv[j][r] = ok ? t[r] : (p.bias_mul ? 1.f : 0.f);
   }
-  if constexpr (EPI == MX_EPI_GEGLU || EPI == MX_EPI_GEGLU_MX) {
+  if constexpr (EPI == MX_EPI_QKV8) {
+    // q|k|v as the packed e4m3 operands of pm_attention_fp8_packed (layout: include/pandora_mi355x.h).  A wave's 64 x 64 piece is
+    // ONE (batch item, part, head, 64-token tile): P % 64 == 0 keeps its rows inside a batch item and on a tile boundary, and
+    // inner = heads * 64 keeps its columns inside one head of one part - whatever the 128-column tile straddles.  The codes go
+    // through the wave's own slice of the staging LDS (idle after the K loop; the loop's last barrier has retired every read of
+    // it), so that they leave as 16-byte stores: Q / K tiles are 4 KiB contiguous, V^T tiles 64 rows of 64 bytes.
+    const int mw0 = m0 + wm * 64;
+    if (mw0 >= p.M) return;  // (M % 128 == 64: the lower half of the last tile lies outside; M % 64 == 0)
+    const int inner = p.heads * 64;
+    const int part = nw0 / inner, head = (nw0 - part * inner) >> 6;
+    const int b = mw0 / p.P, t0 = mw0 - b * p.P;
+    const int64_t bh = (int64_t)b * p.heads + head;
+    uint8_t* const wl = &lds[0][0][0] + wave * 4096;
+    const float mul = part == 0 ? p.qmul : 1.0f;
+    uint32_t code[4][4];  // [i][j]: row 16 i + fr, bytes = columns 16 j + 4 fq + 0..3
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float y = p.bias_mul ? acc[i][j][r] * bv[j][r] : acc[i][j][r] + bv[j][r];
+          if (part == 0) y *= mul;
+          w |= e4m3_sat(y) << (8 * r);
+        }
+        code[i][j] = w;
+      }
+    if (part < 2) {
+      // rows of 64 bytes, the 16-byte chunk XOR-ed with (row >> 2) & 3: dword writes and 16-byte reads without bank conflicts
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 16 * i + fr;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<uint32_t*>(wl + row * 64 + ((j ^ ((row >> 2) & 3)) << 4) + 4 * fq) = code[i][j];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      uint8_t* dst = (part == 0 ? p.q8 : p.k8) + (bh * p.P + t0) * 64;
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        const int row = 16 * it + (lane >> 2), ch = lane & 3;
+        const u32x4 t = *reinterpret_cast<const u32x4*>(wl + row * 64 + ((ch ^ ((row >> 2) & 3)) << 4));
+        st_global16(dst + row * 64 + ch * 16, t);
+      }
+    } else {
+      // V^T: byte (key, d) -> row d, byte pos(key) = 32 ((key >> 2) & 1) + 4 (key >> 3) + (key & 3) of the 64-key tile
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = 16 * i + fr;
+        const int pos = 32 * ((key >> 2) & 1) + 4 * (key >> 3) + (key & 3);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) wl[(16 * j + 4 * fq + r) * 64 + pos] = (uint8_t)(code[i][j] >> (8 * r));
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      uint8_t* dst = p.v8t + bh * 64 * p.P + t0;
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        const int d = 16 * it + (lane >> 2), ch = lane & 3;
+        const u32x4 t = *reinterpret_cast<const u32x4*>(wl + d * 64 + ch * 16);
+        st_global16(dst + (int64_t)d * p.P + ch * 16, t);
+      }
+    }
+  } else if constexpr (EPI == MX_EPI_GEGLU || EPI == MX_EPI_GEGLU_MX) {
     // value block 2jj, gate block 2jj + 1 (weights packed [16 value | 16 gate]); the wave's 32 output columns are ONE MX block
     const int nc = (nw0 >> 1) + 4 * fq;
 #pragma unroll
@@ -483,5 +533,47 @@ extern "C" int pm_gemm_mx8(const void* Aq, int64_t lda, const void* As, int64_t 
     else
       hipLaunchKernelGGL((gemm_mx8_kernel<T, MX_EPI_16>), grid, dim3(256), 0, st, p);
   });
+  return check_launch();
+}
+
+extern "C" int pm_gemm_mx8_qkv_fp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, int64_t ldw,
+                                   const void* Ws, int64_t ldws, const float* bias, void* q8, void* k8, void* v8t, int64_t M,
+                                   int64_t K, int64_t heads, int64_t P, float qmul, int flags, void* stream) {
+  if (!Aq || !As || !Wq || !Ws || !q8 || !k8 || !v8t) return PM_E_NULL;
+  if (flags & ~PM_FLAG_BIAS_IS_SCALE) return PM_E_SHAPE;
+  const bool bmul = flags & PM_FLAG_BIAS_IS_SCALE;
+  if (bmul && bias == nullptr) return PM_E_SHAPE;
+  if (heads < 1 || heads > 4096 || P < 64 || (P & 63) || M < P || M % P || M > (int64_t)1 << 30 || K < 64 || (K & 63) ||
+      K > (1 << 24))
+    return PM_E_SHAPE;
+  const int64_t N = 3 * heads * 64;
+  if (lda < K || ldw < K || (lda & 15) || (ldw & 15) || ldas < K / 32 || ldws < K / 32 || !aligned(Aq, 16) || !aligned(Wq, 16))
+    return PM_E_SHAPE;
+  if (!aligned(q8, 16) || !aligned(k8, 16) || !aligned(v8t, 16) || (bias != nullptr && !aligned(bias, 16))) return PM_E_SHAPE;
+  Mx8Params p{};
+  p.A = static_cast<const uint8_t*>(Aq);
+  p.lda = lda;
+  p.As = static_cast<const uint8_t*>(As);
+  p.ldas = ldas;
+  p.W = static_cast<const uint8_t*>(Wq);
+  p.ldw = ldw;
+  p.Ws = static_cast<const uint8_t*>(Ws);
+  p.ldws = ldws;
+  p.bias = bias;
+  p.M = (int)M;
+  p.N = (int)N;
+  p.K = (int)K;
+  p.bias_mul = bmul;
+  p.mtiles = (int)((M + MX_BM - 1) / MX_BM);
+  p.ntiles = (int)((N + MX_BN - 1) / MX_BN);
+  p.q8 = static_cast<uint8_t*>(q8);
+  p.k8 = static_cast<uint8_t*>(k8);
+  p.v8t = static_cast<uint8_t*>(v8t);
+  p.heads = (int)heads;
+  p.P = (int)P;
+  p.qmul = qmul;
+  if ((int64_t)p.mtiles * p.ntiles > 0x7fffffff) return PM_E_SHAPE;
+  hipLaunchKernelGGL((gemm_mx8_kernel<f16, MX_EPI_QKV8>), dim3((unsigned)(p.mtiles * p.ntiles)), dim3(256), 0, (hipStream_t)stream,
+                     p);  // (the element type parameter is unused by this flavour)
   return check_launch();
 }

@@ -5,6 +5,7 @@ the stream owner) and enqueues exactly one or two kernels from libpandora_mi355x
 current stream.  Activations are channels-last token matrices [frames*H*W, C] in f16 or bf16.
 There is deliberately no CPU / eager fallback here.
 """
+import collections
 import math
 import os
 
@@ -32,6 +33,10 @@ SELECTIVE_PARITY_SITES = frozenset(
                                                                             ("lnt1", 0), ("lnt2", 0), ("lnt3", 0)])
 
 
+# packed e4m3 attention operands (include/pandora_mi355x.h, "packed fp8 attention operands"): uint8 buffers + their sizes
+PackedQKV = collections.namedtuple("PackedQKV", "q8 k8 v8t B Nq Nk")
+
+
 class HipOps:
     name = "hip"
     supports_graphs = True  # every op only enqueues kernels on the current stream: capturable
@@ -42,7 +47,7 @@ class HipOps:
     q_prescale = 64 ** -0.5 * 1.4426950408889634
 
     def __init__(self, dtype=torch.bfloat16, device="cuda", workspace_mb=256, fp8_attention=False, fp8_min_tokens=2048,
-                 parity=False, diag=False, fp8_linear=False, fp8_linear_min_rows=8192):
+                 parity=False, diag=False, fp8_linear=False, fp8_linear_min_rows=8192, fp8_block=False):
         if dtype not in _DT:
             raise ValueError(f"HipOps supports float16/bfloat16 activations, got {dtype}")
         # diag=True: this op table runs on the -DPM_DIAG build of the library (kernel-variant overrides, tuning
@@ -58,6 +63,16 @@ class HipOps:
         self.fp8_linear_min_rows = int(fp8_linear_min_rows)
         if self.fp8_linear and parity:
             raise ValueError("fp8_linear=True and parity: one is a reduced-precision mode, the other carries extra mantissa")
+        # fp8_block (opt-in, needs both modes above): a spatial self-attention site that would take BOTH gemm_mx8 and attention_fp8
+        # and has P % 64 == 0 runs  ln_quant_mx8 -> gemm_mx8_qkv_fp8 -> attention_fp8_packed(mx_out) -> gemm_mx8 (to_out): the
+        # q|k|v GEMM writes the packed e4m3 attention operands and the attention kernel writes to_out's MXFP8 operand - no 16-bit
+        # q|k|v or attention output, no packing or quantising pass (UNetModel._block).  Every other site is unchanged.
+        self.fp8_block = bool(fp8_block)
+        if self.fp8_block and not (self.fp8_linear and self.fp8_attention):
+            raise ValueError("fp8_block=True fuses the MXFP8 q|k|v projection with the fp8 attention: it needs fp8_linear=True and "
+                             "fp8_attention=True")
+        if self.fp8_block and parity:
+            raise ValueError("fp8_block=True and parity: one is a reduced-precision mode, the other carries extra mantissa")
         if os.environ.get("PANDORA_Q_PRESCALE", "1") == "0":  # (numerics experiments: scale inside the kernel)
             self.q_prescale = None
         # LayerNorm + projection pairs of the shallow levels as ONE kernel (pm_ln_gemm); "0": the two-kernel pair (A/B)
@@ -595,6 +610,53 @@ class HipOps:
                                        _ptr(ws), ws.numel(), self._stream())
         capi.check(rc, f"pm_attention_fp8 B={B} heads={heads} Nq={Nq} Nk={Nk}")
         return out
+
+    def gemm_mx8_qkv_fp8(self, a, w, col_scale, heads, P, bias=None, qmul=1.0):
+        """The q|k|v projection of a spatial self-attention in MXFP8, written as the packed e4m3 operands of the fp8 attention
+        (pm_gemm_mx8_qkv_fp8): a = (e4m3 [B*P, K], scales), w = (e4m3 [3*heads*64, K], scales), col_scale f32 [3*heads*64] (the
+        q prescale; or None, then `bias` is added and `qmul` multiplies the q columns).  -> PackedQKV for attention_fp8_packed.
+        The three buffers live in one per-stream allocation (like attention_fp8's workspace): the result is valid until the next
+        call on this stream.  Raises where the shape is not served (P % 64 != 0): callers route those to gemm_mx8."""
+        (aq, as_), (wq, ws) = a, w
+        M, K = aq.shape
+        N = 3 * heads * 64
+        assert wq.shape == (N, K) and as_.shape == (M, K // 32) and ws.shape == (N, K // 32) and aq.stride(1) == 1
+        assert M % P == 0, (M, P)
+        B = M // P
+        flags = 0
+        if col_scale is not None:
+            assert bias is None and col_scale.dtype == torch.float32 and col_scale.numel() == N
+            bias, flags = col_scale, capi.PM_FLAG_BIAS_IS_SCALE
+        part = B * heads * P * 64
+        key = ("fp8_packed", self._stream())
+        buf = self._workspaces.get(key)
+        if buf is None or buf.numel() < 3 * part:
+            buf = self._workspaces[key] = torch.empty(3 * part, dtype=torch.uint8, device=self.device)
+        q8, k8, v8t = buf[:part], buf[part:2 * part], buf[2 * part:3 * part]
+        rc = self.lib.pm_gemm_mx8_qkv_fp8(_ptr(aq), aq.stride(0), _ptr(as_), as_.stride(0), _ptr(wq), wq.stride(0), _ptr(ws),
+                                          ws.stride(0), _ptr(bias), _ptr(q8), _ptr(k8), _ptr(v8t), M, K, heads, P, float(qmul),
+                                          flags, self._stream())
+        capi.check(rc, f"pm_gemm_mx8_qkv_fp8 M={M} K={K} heads={heads} P={P}")
+        return PackedQKV(q8, k8, v8t, B, P, P)
+
+    def attention_fp8_packed(self, packed, heads, out=None, mx_out=False):
+        """The fp8 attention kernel on packed operands (pm_attention_fp8_packed), no packing pass: -> out [B, Nq, heads*64] 16-bit,
+        or with mx_out=True the MXFP8 pair (e4m3 [B*Nq, heads*64], scales [B*Nq, heads*2]) - gemm_mx8's A operand (to_out)."""
+        q8, k8, v8t, B, Nq, Nk = packed
+        C = heads * 64
+        if mx_out:
+            assert out is None
+            o, os_ = self._mx8_pair(B * Nq, C)
+            rc = self.lib.pm_attention_fp8_packed(_ptr(q8), _ptr(k8), _ptr(v8t), Nq, Nk, _ptr(o), Nq * C, C, _ptr(os_),
+                                                  Nq * (C // 32), C // 32, B, heads, self.dt | capi.PM_OUT_MX8, self._stream())
+        else:
+            if out is None:
+                out = self.empty(B, Nq, C)
+            assert out.stride(2) == 1 and out.dtype == self.dtype
+            rc = self.lib.pm_attention_fp8_packed(_ptr(q8), _ptr(k8), _ptr(v8t), Nq, Nk, _ptr(out), out.stride(0), out.stride(1),
+                                                  None, 0, 0, B, heads, self.dt, self._stream())
+        capi.check(rc, f"pm_attention_fp8_packed B={B} heads={heads} Nq={Nq} Nk={Nk}")
+        return (o, os_) if mx_out else out
 
     def attention_generic(self, q, k, v, heads, out=None):
         """Any head dim <= 128 (pm_attention_generic): q [B, Nq, heads*D], k / v [B, Nk, heads*D] views, Nk <= 1024."""

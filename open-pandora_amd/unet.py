@@ -537,6 +537,16 @@ class UNetModel(packing.PackedWeights, nn.Module):
             if key in e:  # self-attention, fused q|k|v projection
                 qs = e.get("a1_qscale") if which == 1 else None
                 self._site(c, f"ln{'t' if temporal else 's'}{which}")
+                # fp8_block: a spatial site that would take BOTH gemm_mx8 and attention_fp8 (and has whole 64-token tiles) runs
+                # them as one chain - the q|k|v GEMM writes the attention's packed e4m3 operands, the attention writes to_out's
+                # MXFP8 operand: no 16-bit q|k|v / attention output, no packing or quantising pass
+                if (mx is not None and not temporal and getattr(ops, "fp8_block", False) and getattr(ops, "fp8_attention", False)
+                        and P >= ops.fp8_min_tokens and P % 64 == 0):
+                    packed = ops.gemm_mx8_qkv_fp8(ops.ln_quant_mx8(h, *ln), mx[key], qs, heads, P,
+                                                  qmul=1.0 if qs is not None else 64 ** -0.5 * 1.4426950408889634)
+                    a_mx = ops.attention_fp8_packed(packed, heads, mx_out=True)
+                    h = ops.gemm_mx8(a_mx, mx[f"a{which}_out"], e[f"a{which}_out"][1], residual=h, stream=True)
+                    continue
                 if mx is not None:
                     qkv = v3(ops.gemm_mx8(ops.ln_quant_mx8(h, *ln), mx[key], col_scale=qs), 3 * inner)
                 else:
