@@ -36,6 +36,22 @@ void pm_debug_gemm_wstream(int mode);
  * epilogues, -, K-steps walked, end-of-kernel s_memtime and s_memrealtime.  `buf`: device memory of 64 bytes x grid size; NULL = off. */
 void pm_debug_wide_stamps(void* buf);
 
+/* The ring-family switches of pm_gemm / the conv entry points (choose_kernel in csrc/gemm.hip) as a setter: `ring` = PANDORA_GEMM_RING
+ * (0 = never, 1 = by the measured rule, 2 = always), `ringw` = PANDORA_GEMM_RINGW (0 / 1; 2 together with ring = 2: every unsplit
+ * 16-bit call on the 256x128 ring kernel), `split_force` = PANDORA_SPLITK_FORCE (0 = the library's own split-K plan, s > 0: every
+ * splittable call takes up to s slices).  -1 leaves a value as it is.  The initial values are 1, 1, 0 unless the environment sets
+ * them (read once, before the first change made here).  Process-wide, as pm_debug_gemm_wide: measurement runs and the forced-kernel
+ * tests, which restore (1, 1, 0). */
+void pm_debug_gemm_ring(int ring, int ringw, int split_force);
+
+/* Which kernel a conv call of this geometry runs on, by the entry point's own plan (the same argument checks, GemmParams, split-K
+ * plan and choose_kernel as the launch): `kind` 0 = pm_conv2d_3x3 on F frames of H x W pixels, 1 = pm_conv_temporal_k3(_clips) on F
+ * frames of P = H x W pixels (stride / upsample2x / pad_lo ignored).  Contiguous operands, no residual, no statistics; `flags` and
+ * `workspace_bytes` as the call would be given.  Returns a pm_gemm_kernel_choice code (0 = 2-stage, 1 = ring, 3 = 256x128 ring) or
+ * the negative PM_E* code the call itself would return. */
+int pm_debug_conv_kernel_choice(int kind, int64_t F, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int stride, int upsample2x,
+                                int pad_lo, int flags, size_t workspace_bytes);
+
 /* The epilogues' erf / GELU approximant (csrc/common.hpp: Q(t) = 2^P(t), r06) element by element over n f32 values:
  * mode 0 = erf(x), mode 1 = gelu(x) = 0.5 x (1 + erf(x / sqrt 2)) (attention.py:415-430, F.gelu).  Returns a PM_* code. */
 int pm_debug_erf(const float* x, float* y, int64_t n, int mode, void* stream);

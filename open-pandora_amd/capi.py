@@ -108,6 +108,9 @@ DIAG_SIGNATURES = {
     "pm_debug_gemm_wstream": (None, [c_int]),
     "pm_debug_wide_stamps": (None, [c_void_p]),
     "pm_debug_erf": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "pm_debug_gemm_ring": (None, [c_int, c_int, c_int]),
+    "pm_debug_conv_kernel_choice": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
+                                            c_size_t]),
 }
 
 _lib = None

@@ -347,11 +347,15 @@ extern "C" int pm_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, c
   PM_DISPATCH_DTYPE(dtype, T, return (launch<T, A_DENSE>(p, flags, (hipStream_t)stream)));
 }
 
-extern "C" int pm_conv2d_3x3(const void* x, int64_t ldx, const void* Wp, const float* bias,
-                             const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t F,
-                             int64_t H, int64_t W, int64_t Cin, int64_t Cout, int stride,
-                             int upsample2x, int pad_lo, const void* zero_page, int flags, int dtype,
-                             void* workspace, size_t workspace_bytes, float* colstats, void* stream) {
+namespace pm {
+
+// The planned call of pm_conv2d_3x3: argument checks, GemmParams, the split plan and the loader mode (`amode`: A_CONV3X3_FAST
+// or A_CONV3X3).  The ONE place a 3x3 conv's parameters are built: the entry point launches what this returns and the
+// diagnostics build's pm_debug_conv_kernel_choice asks choose_kernel about the same thing.
+static int plan_conv3x3(GemmParams& p, int& amode, const void* x, int64_t ldx, const void* Wp, const float* bias,
+                        const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t F, int64_t H, int64_t W, int64_t Cin,
+                        int64_t Cout, int stride, int upsample2x, int pad_lo, const void* zero_page, int flags, void* workspace,
+                        size_t workspace_bytes, float* colstats) {
   if (!zero_page) return PM_E_NULL;
   if (stride != 1 && stride != 2) return PM_E_SHAPE;
   if (upsample2x && stride != 1) return PM_E_SHAPE;
@@ -364,7 +368,7 @@ extern "C" int pm_conv2d_3x3(const void* x, int64_t ldx, const void* Wp, const f
   const int64_t M = F * Ho * Wo, K = 9 * Cin;
   int rc = check_common(x, Wp, y, M, Cout, K, PM_ACT_NONE);
   if (rc) return rc;
-  GemmParams p{};
+  p = GemmParams{};
   p.A = x; p.lda = ldx; p.Wt = Wp; p.ldw = K; p.bias = bias; p.R = residual; p.ldr = ldr;
   p.C = y; p.ldc = ldy; p.M = (int)M; p.N = (int)Cout; p.K = (int)K; p.act = PM_ACT_NONE;
   if ((rc = fill_epilogue(p, flags, colstats)) != PM_OK) return rc;
@@ -376,8 +380,51 @@ extern "C" int pm_conv2d_3x3(const void* x, int64_t ldx, const void* Wp, const f
     p.tap_a[t] = ((int64_t)(t / 3 - 1) * W + (t % 3 - 1)) * ldx * 2;
     p.tap_w[t] = (int64_t)t * Cin * 2;
   }
-  if ((rc = plan_checked(p, workspace, workspace_bytes, /*two_stage=*/upsample2x || (Cin % BK) != 0)) != PM_OK) return rc;
-  if (!upsample2x && (Cin % BK) == 0)
+  amode = (!upsample2x && (Cin % BK) == 0) ? A_CONV3X3_FAST : A_CONV3X3;
+  return plan_checked(p, workspace, workspace_bytes, /*two_stage=*/amode == A_CONV3X3);
+}
+
+// The same for pm_conv_temporal_k3_clips (loader mode A_CONVT3).
+static int plan_conv_temporal(GemmParams& p, const void* x, int64_t ldx, const void* halo_lo, const void* halo_hi, const void* Wp,
+                              const float* bias, const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t F,
+                              int64_t clip_frames, int64_t P, int64_t Cin, int64_t Cout, const void* zero_page, int flags,
+                              void* workspace, size_t workspace_bytes, float* colstats) {
+  if (!zero_page) return PM_E_NULL;
+  if (clip_frames < 1 || F % clip_frames) return PM_E_SHAPE;
+  if (clip_frames != F && (halo_lo || halo_hi)) return PM_E_SHAPE;  // (halo frames belong to ONE clip's ends)
+  if ((Cin & 7) || (ldx & ((flags & PM_FLAG_A_F32) ? 3 : 7)) || ldx < Cin) return PM_E_SHAPE;
+  if (Cin % BK) return PM_E_SHAPE;  // one tap per K-tile
+  if (!fits_u32(F * P * ldx, flags)) return PM_E_SHAPE;
+  const int64_t M = F * P, K = 3 * Cin;
+  int rc = check_common(x, Wp, y, M, Cout, K, PM_ACT_NONE);
+  if (rc) return rc;
+  p = GemmParams{};
+  p.A = x; p.lda = ldx; p.Wt = Wp; p.ldw = K; p.bias = bias; p.R = residual; p.ldr = ldr;
+  p.C = y; p.ldc = ldy; p.M = (int)M; p.N = (int)Cout; p.K = (int)K; p.act = PM_ACT_NONE;
+  if ((rc = fill_epilogue(p, flags, colstats)) != PM_OK) return rc;
+  p.Cin = (int)Cin; p.F = (int)F; p.Fc = (int)clip_frames; p.P = (int)P; p.halo_lo = halo_lo; p.halo_hi = halo_hi;
+  p.zero = zero_page;
+  p.a_bytes = ((F * P - 1) * ldx + Cin) * ((flags & PM_FLAG_A_F32) ? 4 : 2);
+  for (int t = 0; t < 3; ++t) {
+    p.tap_a[t] = (int64_t)(t - 1) * P * ldx * 2;
+    p.tap_w[t] = (int64_t)t * Cin * 2;
+  }
+  return plan_checked(p, workspace, workspace_bytes);
+}
+
+}  // namespace pm
+
+extern "C" int pm_conv2d_3x3(const void* x, int64_t ldx, const void* Wp, const float* bias,
+                             const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t F,
+                             int64_t H, int64_t W, int64_t Cin, int64_t Cout, int stride,
+                             int upsample2x, int pad_lo, const void* zero_page, int flags, int dtype,
+                             void* workspace, size_t workspace_bytes, float* colstats, void* stream) {
+  GemmParams p;
+  int amode = A_CONV3X3;
+  const int rc = plan_conv3x3(p, amode, x, ldx, Wp, bias, residual, ldr, y, ldy, F, H, W, Cin, Cout, stride, upsample2x, pad_lo,
+                              zero_page, flags, workspace, workspace_bytes, colstats);
+  if (rc != PM_OK) return rc;
+  if (amode == A_CONV3X3_FAST)
     PM_DISPATCH_DTYPE(dtype, T, return (launch<T, A_CONV3X3_FAST>(p, flags, (hipStream_t)stream)));
   PM_DISPATCH_DTYPE(dtype, T, return (launch<T, A_CONV3X3>(p, flags, (hipStream_t)stream)));
 }
@@ -398,29 +445,41 @@ extern "C" int pm_conv_temporal_k3_clips(const void* x, int64_t ldx, const void*
                                          int64_t F, int64_t clip_frames, int64_t P, int64_t Cin, int64_t Cout,
                                          const void* zero_page, int flags, int dtype, void* workspace,
                                          size_t workspace_bytes, float* colstats, void* stream) {
-  if (!zero_page) return PM_E_NULL;
-  if (clip_frames < 1 || F % clip_frames) return PM_E_SHAPE;
-  if (clip_frames != F && (halo_lo || halo_hi)) return PM_E_SHAPE;  // (halo frames belong to ONE clip's ends)
-  if ((Cin & 7) || (ldx & ((flags & PM_FLAG_A_F32) ? 3 : 7)) || ldx < Cin) return PM_E_SHAPE;
-  if (Cin % BK) return PM_E_SHAPE;  // one tap per K-tile
-  if (!fits_u32(F * P * ldx, flags)) return PM_E_SHAPE;
-  const int64_t M = F * P, K = 3 * Cin;
-  int rc = check_common(x, Wp, y, M, Cout, K, PM_ACT_NONE);
-  if (rc) return rc;
-  GemmParams p{};
-  p.A = x; p.lda = ldx; p.Wt = Wp; p.ldw = K; p.bias = bias; p.R = residual; p.ldr = ldr;
-  p.C = y; p.ldc = ldy; p.M = (int)M; p.N = (int)Cout; p.K = (int)K; p.act = PM_ACT_NONE;
-  if ((rc = fill_epilogue(p, flags, colstats)) != PM_OK) return rc;
-  p.Cin = (int)Cin; p.F = (int)F; p.Fc = (int)clip_frames; p.P = (int)P; p.halo_lo = halo_lo; p.halo_hi = halo_hi;
-  p.zero = zero_page;
-  p.a_bytes = ((F * P - 1) * ldx + Cin) * ((flags & PM_FLAG_A_F32) ? 4 : 2);
-  for (int t = 0; t < 3; ++t) {
-    p.tap_a[t] = (int64_t)(t - 1) * P * ldx * 2;
-    p.tap_w[t] = (int64_t)t * Cin * 2;
-  }
-  if ((rc = plan_checked(p, workspace, workspace_bytes)) != PM_OK) return rc;
+  GemmParams p;
+  const int rc = plan_conv_temporal(p, x, ldx, halo_lo, halo_hi, Wp, bias, residual, ldr, y, ldy, F, clip_frames, P, Cin, Cout,
+                                    zero_page, flags, workspace, workspace_bytes, colstats);
+  if (rc != PM_OK) return rc;
   PM_DISPATCH_DTYPE(dtype, T, return (launch<T, A_CONVT3>(p, flags, (hipStream_t)stream)));
 }
+
+#ifdef PM_DIAG
+// Diagnostics build: the ring-family switches as a setter (the environment is read once per process) and the conv entry points'
+// own kernel decision as a query (include/pandora_mi355x_diag.h).
+extern "C" void pm_debug_gemm_ring(int ring, int ringw, int split_force) {
+  init_once();  // (first: a later first use must not overwrite these with the environment's values)
+  if (ring >= 0) g_ring = ring;
+  if (ringw >= 0) g_ringw = ringw;
+  if (split_force >= 0) g_split_force = split_force;
+}
+
+extern "C" int pm_debug_conv_kernel_choice(int kind, int64_t F, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int stride,
+                                           int upsample2x, int pad_lo, int flags, size_t workspace_bytes) {
+  // contiguous operands, no residual, no statistics; the pointers are never dereferenced (only their non-NULLness is checked)
+  static float dummy;
+  void* const d = &dummy;
+  GemmParams p;
+  int amode = A_CONVT3, rc;
+  if (kind == 0)
+    rc = plan_conv3x3(p, amode, d, Cin, d, nullptr, nullptr, 0, d, Cout, F, H, W, Cin, Cout, stride, upsample2x, pad_lo, d, flags,
+                      workspace_bytes ? d : nullptr, workspace_bytes, nullptr);
+  else if (kind == 1)
+    rc = plan_conv_temporal(p, d, Cin, nullptr, nullptr, d, nullptr, nullptr, 0, d, Cout, F, F, H * W, Cin, Cout, d, flags,
+                            workspace_bytes ? d : nullptr, workspace_bytes, nullptr);
+  else
+    return PM_E_SHAPE;
+  return rc != PM_OK ? rc : (int)choose_kernel(p, flags, amode);
+}
+#endif
 
 extern "C" int pm_gemm_colstats_rows(int64_t M, int64_t N, int64_t K, int act, size_t workspace_bytes) {
   int ktps;

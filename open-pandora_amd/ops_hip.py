@@ -371,7 +371,8 @@ class HipOps:
         cout = wp.shape[0]
         assert x.shape[0] == F * P and wp.shape[1] == 3 * cin and wp.is_contiguous()
         for h in (halo_lo, halo_hi):
-            assert h is None or (h.shape == (P, cin) and self._rows(h) == self._rows(x))
+            # (the kernel reads a halo frame with x's element type and row stride: a 16-bit halo beside an f32 x would be over-read)
+            assert h is None or (h.shape == (P, cin) and h.dtype == x.dtype and self._rows(h, True) == self._rows(x, True))
         flags, out = self._gemm_io(x, residual, out, F * P, cout, stream)
         col = self._stats_begin(F * P, cout, stats, 3 * cin)
         flags |= self._stats_flags(col)

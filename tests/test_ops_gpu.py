@@ -790,6 +790,7 @@ def test_large_m_gemm_conv_tconv(hip_ops_factory, dtype):
     assert rel_err(ops.conv3x3(x.cuda(), wp.cuda(), b2.cuda(), F, H, W), REF.conv3x3(x, wp, b2, F, H, W)) <= TOL[dtype]
     want = REF.conv3x3(x, wp, b2, F, H, W, stride=2)
     assert want.shape[0] == 16 * 20 * 32
+    assert rel_err(ops.conv3x3(x.cuda(), wp.cuda(), b2.cuda(), F, H, W, stride=2), want) <= TOL[dtype]
     # temporal conv 16 frames x 2560 pixels, 320 channels
     xt = rnd(16 * 2560, 320, dtype=dtype, seed=8)
     wt = rnd(320, 3 * 320, dtype=dtype, scale=960 ** -0.5, seed=9)
