@@ -367,6 +367,45 @@ int pm_gemm_mx8_qkv_fp8(const void* Aq, int64_t lda, const void* As, int64_t lda
                         int64_t ldws, const float* bias, void* q8, void* k8, void* v8t, int64_t M, int64_t K, int64_t heads,
                         int64_t P, float qmul, int flags, void* stream);
 
+/* MXFP8 ResBlock convolutions (opt-in, HipOps(fp8_conv=True)): the GroupNorm + SiLU in front of a conv writes its MXFP8 operand,
+ * and the conv runs on the block-scaled MFMA with the A-loader gathering the taps' neighbour rows.
+ *
+ * pm_groupnorm_apply_mx8: pm_groupnorm_apply with an MXFP8 result - GroupNorm32 + SiLU of ResBlock.in_layers / out_layers
+ * (openaimodel3d.py:154-158,178-183) and of TemporalConvBlock (:258-269).  The f32 value fmaf(x, rstd * gamma, beta - mean * rstd *
+ * gamma), then SiLU if `silu`, is quantised by the rule above: no 16-bit value in between.  q e4m3 [NI*P, C] (ldq % 8 == 0, 8-byte
+ * aligned), scales [NI*P, C/32] (lds).  totals / groups / count / in_dtype as pm_groupnorm_apply; `totals_mode` carries what
+ * pm_groupnorm_apply reads from its out_dtype besides the type: 0 (f32 totals [NI][groups][2]), PM_TOTALS_I64 | nsum << 16 (int64
+ * limbs, nsum entries summed per instance) or n << 16 with n >= 2 (f32 entries summed).  C % 32 == 0; any other bit in
+ * totals_mode (PM_OUT_HILO) returns PM_E_SHAPE.
+ */
+int pm_groupnorm_apply_mx8(const void* x, int64_t ldx, const float* totals, const float* gamma, const float* beta, void* q,
+                           int64_t ldq, void* scales, int64_t lds, int64_t NI, int64_t P, int64_t C, int groups, double count,
+                           float eps, int silu, int in_dtype, int totals_mode, void* stream);
+
+/* pm_conv2d_3x3_mx8 / pm_conv_temporal_k3_mx8: pm_conv2d_3x3 (stride 1, pad_lo 1, no upsample: ResBlock's two 3x3 convs) and
+ * pm_conv_temporal_k3_clips (TemporalConvBlock's 3-tap convs over frames) on MXFP8 operands, as two A-loader modes of pm_gemm_mx8.
+ *   Aq e4m3 [F*H*W, Cin] or [F*P, Cin] (lda % 16 == 0, 16-byte aligned), As its scales [rows, Cin/32] (ldas).
+ *   Wq e4m3 [Cout, taps*Cin], contiguous, the packed conv weight (tap-major K: k = tap * Cin + channel, tap = 3 dy + dx for the
+ *   3x3, tap = frame offset + 1 for the temporal conv); Ws [Cout, taps*Cin/32]: quantised along K, so a block is 32 channels of
+ *   one tap.
+ *   K order: that of pm_gemm_mx8 on the im2col operand - K index k reads channel k % Cin of the row that tap k / Cin points at,
+ *   and the scale of its 32-block from block (k % Cin) / 32 of that row.  Padding: a tap outside the frame (3x3), or outside the
+ *   clip of clip_frames frames (temporal; padding at both ends of every clip, F % clip_frames == 0, no halo frames), contributes
+ *   zero elements with scale 2^0.  The result equals pm_gemm_mx8 (PM_FLAG_OUT_F32) on that im2col operand bit for bit.
+ *   Epilogue: f32 C [rows, Cout] (ldc % 4 == 0, 16-byte aligned) = acc + bias (f32 [Cout], may be NULL) + residual (f32, may be
+ *   NULL): `flags` must be exactly PM_FLAG_OUT_F32 and `act` PM_ACT_NONE.  `dtype` PM_F16 / PM_BF16 (the activation type of the
+ *   caller; no 16-bit tensor is touched).
+ *   Served: Cin % 32 == 0, Cout % 32 == 0, rows <= 2^30.  Everything else - 16-bit output, PM_FLAG_BIAS_IS_SCALE, PM_ACT_GEGLU,
+ *   PM_FLAG_STATS_I64 or any other flag, stride 2, upsampling, pad_lo != 1, PM_OUT_HILO - returns PM_E_SHAPE.  No split-K and no
+ *   fused GroupNorm column sums.
+ */
+int pm_conv2d_3x3_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, const void* Ws, const float* bias,
+                      const void* residual, int64_t ldr, void* C, int64_t ldc, int64_t F, int64_t H, int64_t W, int64_t Cin,
+                      int64_t Cout, int stride, int upsample2x, int pad_lo, int act, int flags, int dtype, void* stream);
+int pm_conv_temporal_k3_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, const void* Ws,
+                            const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, int64_t F,
+                            int64_t clip_frames, int64_t P, int64_t Cin, int64_t Cout, int act, int flags, int dtype, void* stream);
+
 /* (Diagnostics - kernel-variant overrides, ceiling probes, environment tuning switches - are NOT part of this library:
  * they exist only in the -DPM_DIAG build, libpandora_mi355x_diag.so, declared in include/pandora_mi355x_diag.h.  This
  * library reads no environment variable and has no mutable process-wide state.) */

@@ -90,6 +90,14 @@ SIGNATURES = {
                             c_void_p]),
     "pm_gemm_mx8_qkv_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p]),
+    "pm_groupnorm_apply_mx8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                       c_int64, c_int64, c_int64, c_int, c_double, c_float, c_int, c_int, c_int, c_void_p]),
+    "pm_conv2d_3x3_mx8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                  c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, c_void_p]),
+    "pm_conv_temporal_k3_mx8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+                                        c_void_p]),
     "pm_peer_mailbox_bytes": (c_size_t, [c_int, c_int64, c_int64]),
     "pm_peer_create": (c_int, [c_size_t, c_void_p, c_void_p, c_void_p]),
     "pm_peer_open": (c_int, [c_void_p, c_void_p]),

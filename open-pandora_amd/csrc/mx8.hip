@@ -10,36 +10,7 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-// ---- the quantisation rule: mx8_exp / mx8_inv_scale / e4m3_rne of mx8_common.hpp -------------------------------------------
-// One block of 32 values spread over 4 lanes (8 each) that differ in lane-index bits O1 and O2: E8M0 code of the block and the
-// 8 e4m3 codes of this lane (two little-endian words).  A block holding a NaN or an Inf: code 0xFF and NaN (0x7F) elements.
-template <int O1, int O2>
-__device__ __forceinline__ uint32_t mx8_block(const float (&v)[8], uint32_t& w0, uint32_t& w1) {
-  float amax = 0.f;
-  int bad = 0;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    amax = fmaxf(amax, fabsf(v[e]));
-    bad |= finite_f(v[e]) ? 0 : 1;
-  }
-  amax = fmaxf(amax, __shfl_xor(amax, O1, 64));
-  amax = fmaxf(amax, __shfl_xor(amax, O2, 64));
-  bad |= __shfl_xor(bad, O1, 64);
-  bad |= __shfl_xor(bad, O2, 64);
-  if (bad) {
-    w0 = w1 = 0x7f7f7f7fu;
-    return 0xffu;
-  }
-  const int X = mx8_exp(amax);
-  const float inv = mx8_inv_scale(X);
-  uint32_t c[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) c[e] = e4m3_rne(v[e] * inv);  // (exact product: a power of two, result >= 2^-126 or irrelevant)
-  w0 = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
-  w1 = c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24);
-  return (uint32_t)(X + 127);
-}
-
+// ---- the quantisation rule: mx8_exp / mx8_inv_scale / e4m3_rne / mx8_block of mx8_common.hpp -----------------------------
 template <typename TI>
 __device__ __forceinline__ void load8(const TI* p, float (&v)[8]) {
   Pack8<TI> t;
@@ -156,6 +127,13 @@ constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 128;
 constexpr int MX_TILE = MX_BM * MX_BK;  // bytes per operand and buffer
 
 enum { MX_EPI_16 = 0, MX_EPI_F32 = 1, MX_EPI_GEGLU = 2, MX_EPI_GEGLU_MX = 3, MX_EPI_QKV8 = 4 };
+// A-loader modes.  MX_LD_DENSE: A is [M, K].  MX_LD_C3 / MX_LD_T3 (pm_conv2d_3x3_mx8 / pm_conv_temporal_k3_mx8): A is the MXFP8
+// activation [rows, Cin] and K index k is channel k % Cin of tap k / Cin, read from the tap's neighbour row (3x3: pixel
+// (y + tap / 3 - 1, x + tap % 3 - 1) of the same frame; temporal: the same pixel of frame f + tap - 1 of the same clip).  With
+// Cin % 32 == 0 a 16-byte chunk and a 32-block lie inside one tap, a 128-byte K-step does not (Cin = 320: 2.5 steps per tap,
+// Cin = 64: two taps per step): the tap is looked up per chunk and per scale block.  A tap outside the frame / clip is padding:
+// zero elements with scale 2^0, exactly what a zero-filled im2col operand would hold - the K walk is pm_gemm_mx8's.
+enum { MX_LD_DENSE = 0, MX_LD_C3 = 1, MX_LD_T3 = 2 };
 
 struct Mx8Params {
   const uint8_t* A;
@@ -183,11 +161,37 @@ struct Mx8Params {
   uint8_t* v8t;
   int heads, P;  // tokens per batch item (P % 64 == 0, M = B * P)
   float qmul;    // extra factor on the q columns (1 when the prescale arrives as the column scale)
+  // MX_LD_C3 / MX_LD_T3 only (appended likewise)
+  int cin;       // channels per tap (K = taps * cin)
+  int fh, fw;    // 3x3: frame height and width (row m = (f * fh + y) * fw + x)
+  int px, clip;  // temporal: pixels per frame (row m = f * px + pixel) and frames per clip
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * MX_BK + ((chunk ^ (row & 7)) << 4); }
 
-template <typename T, int EPI>
+// conv loaders: bit t of the mask = tap t of row m reads a real row (else padding); tap_rows = how many rows further it lies
+template <int LD>
+__device__ __forceinline__ int tap_mask(const Mx8Params& p, int m) {
+  if constexpr (LD == MX_LD_C3) {
+    const int rem = m % (p.fh * p.fw), y = rem / p.fw, x = rem - y * p.fw;
+    const int xm = (x > 0 ? 1 : 0) | 2 | (x < p.fw - 1 ? 4 : 0);
+    return (y > 0 ? xm : 0) | (xm << 3) | (y < p.fh - 1 ? xm << 6 : 0);
+  } else {
+    const int fi = (m / p.px) % p.clip;
+    return (fi > 0 ? 1 : 0) | 2 | (fi < p.clip - 1 ? 4 : 0);
+  }
+}
+template <int LD>
+__device__ __forceinline__ int tap_rows(const Mx8Params& p, int tap) {
+  if constexpr (LD == MX_LD_C3) {
+    const int dy = tap / 3;
+    return (dy - 1) * p.fw + (tap - 3 * dy - 1);
+  } else {
+    return (tap - 1) * p.px;
+  }
+}
+
+template <typename T, int EPI, int LD = MX_LD_DENSE>
 __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(Mx8Params p) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[2][2][MX_TILE];  // [buffer][A, W]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -211,6 +215,14 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(Mx8Params p) {
     gw[q] = p.W + (int64_t)wr * p.ldw + ch * 16;
     lo[q] = swz(row, ch);
   }
+  int qmask[4], smask[4];  // conv loaders: tap masks of the staged rows and of the fragments' scale rows
+  if constexpr (LD != MX_LD_DENSE) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      qmask[q] = tap_mask<LD>(p, min(m0 + ((tid + 256 * q) >> 3), p.M - 1));
+      smask[q] = tap_mask<LD>(p, min(m0 + wm * 64 + q * 16 + fr, p.M - 1));
+    }
+  }
   // scale rows of this lane's fragments
   const uint8_t* sa[4];
   const uint8_t* sw[4];
@@ -224,18 +236,40 @@ __global__ __launch_bounds__(256, 2) void gemm_mx8_kernel(Mx8Params p) {
   int xa[4], xw[4];
   auto fetch = [&](int kt) {
     const int k0 = kt * MX_BK;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int ch = (tid + 256 * q) & 7;
-      const bool in = k0 + ch * 16 < p.K;
-      ra[q] = in ? ld_global16(ga[q] + k0) : u32x4{0u, 0u, 0u, 0u};
-      rw[q] = in ? ld_global16(gw[q] + k0) : u32x4{0u, 0u, 0u, 0u};
-    }
     const int kb = kt * 4 + fq;  // past K (zero-filled half step): any finite scale, 2^0
+    if constexpr (LD == MX_LD_DENSE) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      xa[i] = kb < kblocks ? (int)sa[i][kb] : 127;
-      xw[i] = kb < kblocks ? (int)sw[i][kb] : 127;
+      for (int q = 0; q < 4; ++q) {
+        const int ch = (tid + 256 * q) & 7;
+        const bool in = k0 + ch * 16 < p.K;
+        ra[q] = in ? ld_global16(ga[q] + k0) : u32x4{0u, 0u, 0u, 0u};
+        rw[q] = in ? ld_global16(gw[q] + k0) : u32x4{0u, 0u, 0u, 0u};
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        xa[i] = kb < kblocks ? (int)sa[i][kb] : 127;
+        xw[i] = kb < kblocks ? (int)sw[i][kb] : 127;
+      }
+    } else {
+      // this thread's chunk (the same column of all four staged rows): tap and channel of its first element
+      const int k = k0 + (tid & 7) * 16;
+      const bool in = k < p.K;
+      const int tap = in ? k / p.cin : 0;
+      const int64_t aoff = (int64_t)tap_rows<LD>(p, tap) * p.lda + (k - tap * p.cin) - (tid & 7) * 16;  // (ga holds ch * 16)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        ra[q] = in && ((qmask[q] >> tap) & 1) ? ld_global16(ga[q] + aoff) : u32x4{0u, 0u, 0u, 0u};
+        rw[q] = in ? ld_global16(gw[q] + k0) : u32x4{0u, 0u, 0u, 0u};
+      }
+      // this lane's scale block 4 kt + fq: block (k % Cin) / 32 of the tap's neighbour row
+      const bool ins = kb < kblocks;
+      const int ks = kb * 32, stap = ins ? ks / p.cin : 0;
+      const int64_t soff = (int64_t)tap_rows<LD>(p, stap) * p.ldas + ((ks - stap * p.cin) >> 5);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        xa[i] = ins && ((smask[i] >> stap) & 1) ? (int)sa[i][soff] : 127;
+        xw[i] = ins ? (int)sw[i][kb] : 127;
+      }
     }
   };
   auto stage = [&](int buf) {
@@ -576,4 +610,73 @@ extern "C" int pm_gemm_mx8_qkv_fp8(const void* Aq, int64_t lda, const void* As, 
   hipLaunchKernelGGL((gemm_mx8_kernel<f16, MX_EPI_QKV8>), dim3((unsigned)(p.mtiles * p.ntiles)), dim3(256), 0, (hipStream_t)stream,
                      p);  // (the element type parameter is unused by this flavour)
   return check_launch();
+}
+
+// ---- pm_conv2d_3x3_mx8 / pm_conv_temporal_k3_mx8: the conv A-loader modes of gemm_mx8_kernel, MX_EPI_F32 epilogue only --------
+// (the element type parameter is unused by that flavour with an f32 residual: one instance per loader)
+template <int LD>
+static int conv_mx8(Mx8Params& p, const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, const void* Ws,
+                    const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, int64_t M, int64_t taps,
+                    int64_t Cin, int64_t Cout, int act, int flags, int dtype, void* stream) {
+  if (!Aq || !As || !Wq || !Ws || !C) return PM_E_NULL;
+  if (dtype & ~0xff) return PM_E_SHAPE;  // (PM_OUT_HILO, PM_OUT_MX8 and any other output mode)
+  if (dtype != PM_F16 && dtype != PM_BF16) return PM_E_DTYPE;
+  // f32 output onto an optional f32 residual and nothing else: 16-bit output, a column scale, statistics flags (and their instance
+  // count), f32 / [hi | lo] A operands are not served
+  if (flags != PM_FLAG_OUT_F32 || act != PM_ACT_NONE) return PM_E_SHAPE;
+  const int64_t K = taps * Cin;
+  if (M < 1 || M > (int64_t)1 << 30 || Cout < 32 || (Cout & 31) || Cout > (1 << 24) || Cin < 32 || (Cin & 31) || K > (1 << 24))
+    return PM_E_SHAPE;
+  if (lda < Cin || (lda & 15) || ldas < Cin / 32 || !aligned(Aq, 16) || !aligned(Wq, 16)) return PM_E_SHAPE;
+  if (ldc < Cout || (ldc & 3) || !aligned(C, 16) || (bias != nullptr && !aligned(bias, 16))) return PM_E_SHAPE;
+  if (residual != nullptr && (ldr < Cout || (ldr & 3) || !aligned(residual, 16))) return PM_E_SHAPE;
+  p.A = static_cast<const uint8_t*>(Aq);
+  p.lda = lda;
+  p.As = static_cast<const uint8_t*>(As);
+  p.ldas = ldas;
+  p.W = static_cast<const uint8_t*>(Wq);  // packed [Cout, taps * Cin], tap-major, contiguous; scales [Cout, taps * Cin / 32]
+  p.ldw = K;
+  p.Ws = static_cast<const uint8_t*>(Ws);
+  p.ldws = K / 32;
+  p.bias = bias;
+  p.R = residual;
+  p.ldr = ldr;
+  p.C = C;
+  p.ldc = ldc;
+  p.M = (int)M;
+  p.N = (int)Cout;
+  p.K = (int)K;
+  p.res32 = 1;
+  p.cin = (int)Cin;
+  p.mtiles = (int)((M + MX_BM - 1) / MX_BM);
+  p.ntiles = (int)((Cout + MX_BN - 1) / MX_BN);
+  if ((int64_t)p.mtiles * p.ntiles > 0x7fffffff) return PM_E_SHAPE;
+  hipLaunchKernelGGL((gemm_mx8_kernel<f16, MX_EPI_F32, LD>), dim3((unsigned)(p.mtiles * p.ntiles)), dim3(256), 0,
+                     (hipStream_t)stream, p);
+  return check_launch();
+}
+
+extern "C" int pm_conv2d_3x3_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, const void* Ws,
+                                 const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, int64_t F, int64_t H,
+                                 int64_t W, int64_t Cin, int64_t Cout, int stride, int upsample2x, int pad_lo, int act, int flags,
+                                 int dtype, void* stream) {
+  if (stride != 1 || upsample2x || pad_lo != 1) return PM_E_SHAPE;  // the fast mode of pm_conv2d_3x3 only
+  if (F < 1 || H < 1 || W < 1 || H > (1 << 30) || W > (1 << 30) || F > (1 << 30) || H * W > (int64_t)1 << 30) return PM_E_SHAPE;
+  Mx8Params p{};
+  p.fh = (int)H;
+  p.fw = (int)W;
+  return conv_mx8<MX_LD_C3>(p, Aq, lda, As, ldas, Wq, Ws, bias, residual, ldr, C, ldc, F * H * W, 9, Cin, Cout, act, flags, dtype,
+                            stream);
+}
+
+extern "C" int pm_conv_temporal_k3_mx8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, const void* Ws,
+                                       const float* bias, const void* residual, int64_t ldr, void* C, int64_t ldc, int64_t F,
+                                       int64_t clip_frames, int64_t P, int64_t Cin, int64_t Cout, int act, int flags, int dtype,
+                                       void* stream) {
+  if (F < 1 || P < 1 || F > (1 << 30) || P > (1 << 30) || clip_frames < 1 || F % clip_frames) return PM_E_SHAPE;
+  Mx8Params p{};
+  p.px = (int)P;
+  p.clip = (int)clip_frames;
+  return conv_mx8<MX_LD_T3>(p, Aq, lda, As, ldas, Wq, Ws, bias, residual, ldr, C, ldc, F * P, 3, Cin, Cout, act, flags, dtype,
+                            stream);
 }

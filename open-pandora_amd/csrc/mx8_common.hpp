@@ -1,5 +1,5 @@
-// The MXFP8 / e4m3 quantisation rule as device code, shared by the MXFP8 GEMM and quantiser (mx8.hip) and the fp8 attention's
-// MXFP8 output (attn.hip).  The rule itself: include/pandora_mi355x.h, "MXFP8"; restated in numpy by tests/test_mx8_cpu.py.
+// The MXFP8 / e4m3 quantisation rule as device code, shared by the MXFP8 GEMM and quantiser (mx8.hip), the fp8 attention's
+// MXFP8 output (attn.hip) and the GroupNorm-apply quantiser (norm.hip).  The rule itself: include/pandora_mi355x.h, "MXFP8"; restated in numpy by tests/test_mx8_cpu.py.
 #pragma once
 #include "common.hpp"
 
@@ -29,6 +29,35 @@ __device__ __forceinline__ uint32_t e4m3_rne(float y) {
   return s | (uint32_t)__builtin_rintf(__uint_as_float(b) * 512.0f);  // 8 -> 0x08 = 2^-6, the smallest normal
 }
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e38f; }  // (false for NaN)
+
+// One block of 32 values spread over 4 lanes (8 each) that differ in lane-index bits O1 and O2: E8M0 code of the block and the
+// 8 e4m3 codes of this lane (two little-endian words).  A block holding a NaN or an Inf: code 0xFF and NaN (0x7F) elements.
+template <int O1, int O2>
+__device__ __forceinline__ uint32_t mx8_block(const float (&v)[8], uint32_t& w0, uint32_t& w1) {
+  float amax = 0.f;
+  int bad = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    amax = fmaxf(amax, fabsf(v[e]));
+    bad |= finite_f(v[e]) ? 0 : 1;
+  }
+  amax = fmaxf(amax, __shfl_xor(amax, O1, 64));
+  amax = fmaxf(amax, __shfl_xor(amax, O2, 64));
+  bad |= __shfl_xor(bad, O1, 64);
+  bad |= __shfl_xor(bad, O2, 64);
+  if (bad) {
+    w0 = w1 = 0x7f7f7f7fu;
+    return 0xffu;
+  }
+  const int X = mx8_exp(amax);
+  const float inv = mx8_inv_scale(X);
+  uint32_t c[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) c[e] = e4m3_rne(v[e] * inv);  // (exact product: a power of two, result >= 2^-126 or irrelevant)
+  w0 = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+  w1 = c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24);
+  return (uint32_t)(X + 127);
+}
 
 // e4m3fn code of ANY f32 (the packed fp8 attention operands, include/pandora_mi355x.h "packed fp8 attention operands"):
 // clamp to +-448 (infinities included), then e4m3_rne; NaN -> 0x7F.

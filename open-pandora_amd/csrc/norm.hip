@@ -3,6 +3,7 @@
 // are 16 bytes per lane along the contiguous channel axis; statistics are f32.
 #include <type_traits>
 #include "gemm_common.hpp"  // (gs_atomic_add / GS_INV_*: the int64 GroupNorm totals, r06)
+#include "mx8_common.hpp"   // (mx8_block: the MXFP8 result of pm_groupnorm_apply_mx8)
 
 namespace pm {
 
@@ -181,11 +182,15 @@ __global__ __launch_bounds__(256) void gn_finalize_colstats_kernel(const float* 
 // nsum > 0 (r06): `totals` are int64 fixed-point limbs [NI * nsum][groups][4] (gemm_common.hpp) and instance i uses the SUM of
 // entries i*nsum .. i*nsum + nsum-1 (per-frame sums of a clip add up to its (T,H,W) sums: exact in integers); nsum < 0: f32
 // {sum, sumsq} entries [NI * -nsum][groups][2] summed the same way (in entry order)
-template <typename TI, typename T>
+// MX (pm_groupnorm_apply_mx8, T = uint8_t, C % 32 == 0): the f32 value is quantised by the MXFP8 rule instead of rounded to 16 bit -
+// y is the e4m3 matrix (ldy bytes per row), ys / ldys its E8M0 scales.  The four adjacent lanes that own a 32-block (CV % 4 == 0:
+// the same row, the same wave, and in or out of every branch together) form it with mx8_block.
+template <typename TI, typename T, bool MX = false>
 __global__ void gn_apply_kernel(const TI* __restrict__ x, int64_t ldx, const float* __restrict__ totals,
                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                 T* __restrict__ y, int64_t ldy, int P, int C, int groups, float inv_count,
-                                float eps, int silu, int rows_per_block, int lo_off, int nsum) {
+                                float eps, int silu, int rows_per_block, int lo_off, int nsum,
+                                uint8_t* __restrict__ ys = nullptr, int64_t ldys = 0) {
   // lo_off != 0 (PM_OUT_HILO, the parity configuration): the row is written as [hi | lo], hi = round16(v) at its
   // column, lo = round16(v - hi) lo_off columns further: a consumer GEMM / conv over 2C channels with the weights
   // repeated sees the normalised activation at ~2x the mantissa
@@ -304,16 +309,29 @@ __global__ void gn_apply_kernel(const TI* __restrict__ x, int64_t ldx, const flo
     for (int u = 0; u < 4; ++u) {
       const int ru = r + u * k;
       if (ru < r1) {
-        Pack8<T> o, lo;
+        if constexpr (MX) {
+          float v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float v = fmaf(t[u][e], sc[e], sh[e]);
-          if (silu) v = silu_f(v);
-          o.e[e] = from_f32<T>(v);
-          lo.e[e] = from_f32<T>(v - to_f32(o.e[e]));
+          for (int e = 0; e < 8; ++e) {
+            v[e] = fmaf(t[u][e], sc[e], sh[e]);
+            if (silu) v[e] = silu_f(v[e]);
+          }
+          uint32_t w0, w1;
+          const uint32_t code = mx8_block<1, 2>(v, w0, w1);
+          *reinterpret_cast<u32x2*>(yp + (int64_t)ru * ldy) = u32x2{w0, w1};
+          if ((cv & 3) == 0) ys[((int64_t)inst * P + ru) * ldys + (cv >> 2)] = (uint8_t)code;
+        } else {
+          Pack8<T> o, lo;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float v = fmaf(t[u][e], sc[e], sh[e]);
+            if (silu) v = silu_f(v);
+            o.e[e] = from_f32<T>(v);
+            lo.e[e] = from_f32<T>(v - to_f32(o.e[e]));
+          }
+          st_global16(yp + (int64_t)ru * ldy, o.u);
+          if (lo_off) st_global16(yp + (int64_t)ru * ldy + lo_off, lo.u);
         }
-        st_global16(yp + (int64_t)ru * ldy, o.u);
-        if (lo_off) st_global16(yp + (int64_t)ru * ldy + lo_off, lo.u);
       }
     }
   }
@@ -532,6 +550,18 @@ extern "C" int pm_groupnorm_finalize_colstats(const float* colstats, float* tota
   return check_launch();
 }
 
+// rows per block of gn_apply_kernel
+static int64_t gn_apply_rows_per_block(int64_t NI, int64_t P, int64_t C, int nsum) {
+  const int threads = gn_threads((int)(C >> 3));
+  const int k = threads / (int)(C >> 3);
+  int64_t rpb = 4 * k;  // one batch of four rows per thread; more only to keep the grid under ~8192 blocks
+  while (((P + rpb - 1) / rpb) * NI > 8192) rpb *= 2;
+  // summed totals: every block adds up the n entries of its instance itself (n x groups x 4 limbs, a 64-byte sector each: 128 KB
+  // of L2 reads per block at n = 16) - four batches per block keep that beside the rows' traffic instead of above it
+  if ((nsum >= 4 || nsum <= -4) && ((P + 4 * rpb - 1) / (4 * rpb)) * NI >= 256) rpb *= 4;
+  return rpb;
+}
+
 extern "C" int pm_groupnorm_apply(const void* x, int64_t ldx, const float* totals,
                                   const float* gamma, const float* beta, void* y, int64_t ldy,
                                   int64_t NI, int64_t P, int64_t C, int groups, double count,
@@ -548,12 +578,7 @@ extern "C" int pm_groupnorm_apply(const void* x, int64_t ldx, const float* total
   out_dtype &= 0xff;
   if ((ldy & 7) || ldy < C + lo_off || count <= 0) return PM_E_SHAPE;
   const int threads = gn_threads((int)(C >> 3));
-  const int k = threads / (int)(C >> 3);
-  int64_t rpb = 4 * k;  // one batch of four rows per thread; more only to keep the grid under ~8192 blocks
-  while (((P + rpb - 1) / rpb) * NI > 8192) rpb *= 2;
-  // summed totals: every block adds up the n entries of its instance itself (n x groups x 4 limbs, a 64-byte sector each: 128 KB
-  // of L2 reads per block at n = 16) - four batches per block keep that beside the rows' traffic instead of above it
-  if ((nsum >= 4 || nsum <= -4) && ((P + 4 * rpb - 1) / (4 * rpb)) * NI >= 256) rpb *= 4;
+  const int64_t rpb = gn_apply_rows_per_block(NI, P, C, nsum);
   dim3 grid((unsigned)((P + rpb - 1) / rpb), (unsigned)NI);
   PM_DISPATCH_IN_OUT(in_dtype, out_dtype, TI, TO,
                      hipLaunchKernelGGL((gn_apply_kernel<TI, TO>), grid, dim3(threads), 0,
@@ -561,6 +586,38 @@ extern "C" int pm_groupnorm_apply(const void* x, int64_t ldx, const float* total
                                         gamma, beta, (TO*)y, ldy, (int)P, (int)C, groups,
                                         (float)(1.0 / count), eps, silu, (int)rpb, lo_off, nsum);
                      return check_launch());
+}
+
+extern "C" int pm_groupnorm_apply_mx8(const void* x, int64_t ldx, const float* totals, const float* gamma, const float* beta,
+                                      void* q, int64_t ldq, void* scales, int64_t lds, int64_t NI, int64_t P, int64_t C, int groups,
+                                      double count, float eps, int silu, int in_dtype, int totals_mode, void* stream) {
+  if (!x || !totals || !gamma || !beta || !q || !scales) return PM_E_NULL;
+  int rc = gn_check(NI, P, C, groups, ldx, in_dtype);
+  if (rc) return rc;
+  if (in_dtype != PM_F16 && in_dtype != PM_BF16 && in_dtype != PM_F32) return PM_E_DTYPE;
+  // totals_mode: PM_TOTALS_I64 and the entry count in bits 16..23, as in pm_groupnorm_apply's out_dtype; nothing else (PM_OUT_HILO)
+  if (totals_mode & ~(PM_TOTALS_I64 | 0xff0000)) return PM_E_SHAPE;
+  int nsum = (totals_mode >> 16) & 0xff;
+  if ((totals_mode & PM_TOTALS_I64) && nsum < 1) return PM_E_SHAPE;
+  if (!(totals_mode & PM_TOTALS_I64)) nsum = nsum >= 2 ? -nsum : 0;
+  if ((C & 31) || (ldq & 7) || ldq < C || lds < C / 32 || count <= 0 || (reinterpret_cast<uintptr_t>(q) & 7) ||
+      (reinterpret_cast<uintptr_t>(x) & 15))
+    return PM_E_SHAPE;
+  const int threads = gn_threads((int)(C >> 3));
+  const int64_t rpb = gn_apply_rows_per_block(NI, P, C, nsum);
+  dim3 grid((unsigned)((P + rpb - 1) / rpb), (unsigned)NI);
+#define PM_GN_MX8(TI)                                                                                                          \
+  hipLaunchKernelGGL((gn_apply_kernel<TI, uint8_t, true>), grid, dim3(threads), 0, (hipStream_t)stream, (const TI*)x, ldx, totals, \
+                     gamma, beta, (uint8_t*)q, ldq, (int)P, (int)C, groups, (float)(1.0 / count), eps, silu, (int)rpb, 0, nsum,   \
+                     (uint8_t*)scales, lds)
+  if (in_dtype == PM_F32)
+    PM_GN_MX8(float);
+  else if (in_dtype == PM_F16)
+    PM_GN_MX8(pm::f16);
+  else
+    PM_GN_MX8(pm::bf16);
+#undef PM_GN_MX8
+  return check_launch();
 }
 
 extern "C" int pm_layernorm(const void* x, int64_t ldx, const float* gamma, const float* beta,

@@ -47,7 +47,8 @@ class HipOps:
     q_prescale = 64 ** -0.5 * 1.4426950408889634
 
     def __init__(self, dtype=torch.bfloat16, device="cuda", workspace_mb=256, fp8_attention=False, fp8_min_tokens=2048,
-                 parity=False, diag=False, fp8_linear=False, fp8_linear_min_rows=8192, fp8_block=False):
+                 parity=False, diag=False, fp8_linear=False, fp8_linear_min_rows=8192, fp8_block=False, fp8_conv=False,
+                 fp8_conv_min_rows=8192):
         if dtype not in _DT:
             raise ValueError(f"HipOps supports float16/bfloat16 activations, got {dtype}")
         # diag=True: this op table runs on the -DPM_DIAG build of the library (kernel-variant overrides, tuning
@@ -73,6 +74,15 @@ class HipOps:
                              "fp8_attention=True")
         if self.fp8_block and parity:
             raise ValueError("fp8_block=True and parity: one is a reduced-precision mode, the other carries extra mantissa")
+        # MXFP8 ResBlock convolutions (opt-in, independent of the modes above): the GroupNorm + SiLU in front of a ResBlock's 3x3
+        # convs and of the TemporalConvBlock's 3-tap convs writes the conv's MXFP8 A operand (pm_groupnorm_apply_mx8: no 16-bit
+        # activation, no quantising pass) and the conv runs on pm_conv2d_3x3_mx8 / pm_conv_temporal_k3_mx8 with weights quantised
+        # once in UNetModel.prepare.  Sites with fewer than `fp8_conv_min_rows` rows, channel counts that are no multiple of 32, or
+        # frame shards (halo frames) stay on the 16-bit kernels (UNetModel._res_block); the default threshold is fp8_linear's
+        self.fp8_conv = bool(fp8_conv)
+        self.fp8_conv_min_rows = int(fp8_conv_min_rows)
+        if self.fp8_conv and parity:
+            raise ValueError("fp8_conv=True and parity: one is a reduced-precision mode, the other carries extra mantissa")
         if os.environ.get("PANDORA_Q_PRESCALE", "1") == "0":  # (numerics experiments: scale inside the kernel)
             self.q_prescale = None
         # LayerNorm + projection pairs of the shallow levels as ONE kernel (pm_ln_gemm); "0": the two-kernel pair (A/B)
@@ -564,6 +574,64 @@ class HipOps:
                                   flags, dt, self._stream())
         capi.check(rc, f"pm_gemm_mx8 M={M} N={N} K={K}")
         return (out, cs) if mx_out else out
+
+    # -- MXFP8 ResBlock convolutions (fp8_conv) -------------------------------------------------------
+    def groupnorm_mx8(self, x, gamma, beta, eps, NI, silu, totals=None, count=None, groups=32):
+        """groupnorm(...) with an MXFP8 result (pm_groupnorm_apply_mx8): -> (e4m3 [M, C] uint8, E8M0 scales [M, C/32] uint8), the A
+        operand of conv3x3_mx8 / conv_t3_mx8.  `totals` as groupnorm_apply takes them (f32, int64 limbs, several entries per
+        instance); None: the statistics pass runs first."""
+        M, C = x.shape
+        P = M // NI
+        assert P * NI == M and C % 32 == 0
+        tot = totals if totals is not None else self.groupnorm_stats(x, NI, groups)
+        if count is None:
+            count = float(P * (C // groups))
+        nsum = tot.shape[0] // NI
+        mode = 0
+        if tot.dtype == torch.int64:
+            assert tot.shape == (NI * nsum, groups, 4, 8) and tot.is_contiguous() and 1 <= nsum <= 255
+            mode = capi.PM_TOTALS_I64 | (nsum << 16)
+        else:
+            assert tot.shape == (NI * nsum, groups, 2) and tot.is_contiguous() and 1 <= nsum <= 255
+            if nsum > 1:
+                mode = nsum << 16
+        q, s = self._mx8_pair(M, C)
+        rc = self.lib.pm_groupnorm_apply_mx8(_ptr(x), self._rows(x, True), _ptr(tot), _ptr(gamma), _ptr(beta), _ptr(q), q.stride(0),
+                                             _ptr(s), s.stride(0), NI, P, C, groups, float(count), float(eps), int(silu),
+                                             self._in_dt(x), mode, self._stream())
+        capi.check(rc, f"pm_groupnorm_apply_mx8 NI={NI} P={P} C={C}")
+        return q, s
+
+    def _conv_mx8_io(self, a, w, taps, rows, residual, out):
+        (aq, as_), (wq, ws) = a, w
+        cin, cout = aq.shape[1], wq.shape[0]
+        assert aq.shape[0] == rows and aq.stride(1) == 1 and as_.shape == (rows, cin // 32) and as_.stride(1) == 1
+        assert wq.shape == (cout, taps * cin) and ws.shape == (cout, taps * cin // 32) and wq.is_contiguous() and ws.is_contiguous()
+        _, out = self._gemm_io(aq, residual, out, rows, cout, True)
+        return aq, as_, wq, ws, cin, cout, out
+
+    def conv3x3_mx8(self, a, w, bias, F, H, W, residual=None, out=None, stats=None):
+        """conv3x3(..., stream=True) (stride 1, pad 1) on MXFP8 operands (pm_conv2d_3x3_mx8): a = (e4m3 [F*H*W, Cin], scales),
+        w = the packed weight [Cout, 9*Cin] through quant_mx8.  -> f32 [F*H*W, Cout] (+ f32 residual); with `stats`, what
+        conv3x3 returns where its epilogue cannot deliver them: the statistics pass over the output, or None for a lazy request."""
+        aq, as_, wq, ws, cin, cout, out = self._conv_mx8_io(a, w, 9, F * H * W, residual, out)
+        rc = self.lib.pm_conv2d_3x3_mx8(_ptr(aq), aq.stride(0), _ptr(as_), as_.stride(0), _ptr(wq), _ptr(ws), _ptr(bias),
+                                        _ptr(residual), residual.stride(0) if residual is not None else 0, _ptr(out),
+                                        out.stride(0), F, H, W, cin, cout, 1, 0, 1, capi.PM_ACT_NONE, capi.PM_FLAG_OUT_F32,
+                                        self.dt, self._stream())
+        capi.check(rc, f"pm_conv2d_3x3_mx8 F={F} H={H} W={W} Cin={cin} Cout={cout}")
+        return self._stats_end(out, None, stats)
+
+    def conv_t3_mx8(self, a, w, bias, F, P, residual=None, out=None, stats=None, clip_frames=None):
+        """conv_t3(..., stream=True) without halo frames on MXFP8 operands (pm_conv_temporal_k3_mx8); w = the packed weight
+        [Cout, 3*Cin] through quant_mx8.  Returns as conv3x3_mx8."""
+        aq, as_, wq, ws, cin, cout, out = self._conv_mx8_io(a, w, 3, F * P, residual, out)
+        rc = self.lib.pm_conv_temporal_k3_mx8(_ptr(aq), aq.stride(0), _ptr(as_), as_.stride(0), _ptr(wq), _ptr(ws), _ptr(bias),
+                                              _ptr(residual), residual.stride(0) if residual is not None else 0, _ptr(out),
+                                              out.stride(0), F, clip_frames or F, P, cin, cout, capi.PM_ACT_NONE,
+                                              capi.PM_FLAG_OUT_F32, self.dt, self._stream())
+        capi.check(rc, f"pm_conv_temporal_k3_mx8 F={F} P={P} Cin={cin} Cout={cout}")
+        return self._stats_end(out, None, stats)
 
     def attention(self, q, k1, v1, heads, k2=None, v2=None, w2=1.0, out=None, prescaled=False):
         """q [B, Nq, heads*64] view; kX/vX [B or 1, NkX, heads*64] views (last dim contiguous).

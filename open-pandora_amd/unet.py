@@ -346,6 +346,14 @@ class UNetModel(packing.PackedWeights, nn.Module):
                     tc = mod.temopral_conv
                     e["tconv"] = [((f32(s[0].weight), f32(s[0].bias)), wt(packing.pack_conv_t3(s[-1].weight)),
                                    f32(s[-1].bias)) for s in (tc.conv1, tc.conv2, tc.conv3, tc.conv4)]
+                if getattr(ops, "fp8_conv", False):
+                    # MXFP8 conv mode: the packed conv weights quantised ONCE along K (tap-major: a block is 32 channels of one
+                    # tap), by the kernel and rule of the activations; None where the channel counts are not served.  The
+                    # 16-bit weights above stay for the sites that fall back (_res_block)
+                    mxq = lambda wp, taps: (ops.quant_mx8(wp) if wp.shape[0] % 32 == 0 and (wp.shape[1] // taps) % 32 == 0
+                                            else None)
+                    e["mx8c"] = {"conv1": mxq(e["conv1"], 9), "conv2": mxq(e["conv2"][0], 9),
+                                 "tconv": [mxq(s[1], 3) for s in e.get("tconv", [])]}
                 W[name] = e
             elif isinstance(mod, _Transformer):
                 blk = mod.transformer_blocks[0]
@@ -420,8 +428,9 @@ class UNetModel(packing.PackedWeights, nn.Module):
         block's attn1 projection / attn2 projection / GEGLU, split = the f32 stream into a Downsample / Upsample / stem conv."""
         c.ops.site = (kind, c.level)
 
-    def _gn(self, c, x, gb, eps, silu, per_frame, totals=None):
-        """`totals`: {sum, sumsq} already produced by the epilogue of the op that wrote x."""
+    def _gn(self, c, x, gb, eps, silu, per_frame, totals=None, mx=False):
+        """`totals`: {sum, sumsq} already produced by the epilogue of the op that wrote x.
+        `mx`: the result is the MXFP8 pair of an MX conv (HipOps(fp8_conv=True); never with frame shards)."""
         ops = c.ops
         self._site(c, ("gn3" if per_frame else "gnt") if silu else "gnp")
         if totals is None:  # statistics a previous module's last op left behind ON this very tensor object
@@ -437,6 +446,8 @@ class UNetModel(packing.PackedWeights, nn.Module):
                         totals = tot  # (int64 limbs or f32 sums alike: entries b T .. b T + T - 1 belong to clip b)
                     else:
                         totals = tot.sum(0, keepdim=True) if c.B == 1 else tot.view(c.B, c.T, *tot.shape[1:]).sum(1)
+        if mx:
+            return ops.groupnorm_mx8(x, gb[0], gb[1], eps, c.F if per_frame else c.B, silu, totals=totals)
         if per_frame:
             return ops.groupnorm(x, gb[0], gb[1], eps, c.F, silu, totals=totals)
         red = c.fp.reduce_stats if c.fp is not None else None
@@ -460,25 +471,34 @@ class UNetModel(packing.PackedWeights, nn.Module):
     def _res_block(self, c, mod, x, out=None):
         ops, e = c.ops, c.w[self._names[mod]]
         P = c.H * c.W
-        h = self._gn(c, x, e["gn1"], 1e-5, True, True)
+        # MXFP8 conv mode (HipOps(fp8_conv=True)): a conv of a site with enough rows, channel counts in multiples of 32 and no frame
+        # shards (they need halo frames) takes its A operand as MXFP8 straight from the GroupNorm + SiLU in front of it and runs
+        # on the MX conv kernels; every other conv, and every other site, makes the calls it made before
+        mxc = e.get("mx8c") if (getattr(ops, "fp8_conv", False) and c.fp is None and c.F * P >= ops.fp8_conv_min_rows) else None
+        m1, m2 = (mxc["conv1"], mxc["conv2"]) if mxc is not None else (None, None)
+        conv2 = ((lambda a, **kw: ops.conv3x3_mx8(a, m2, e["conv2"][1], c.F, c.H, c.W, **kw)) if m2 is not None else
+                 (lambda a, **kw: ops.conv3x3(a, e["conv2"][0], e["conv2"][1], c.F, c.H, c.W, stream=True, **kw)))
+        h = self._gn(c, x, e["gn1"], 1e-5, True, True, mx=m1 is not None)
         lo, hi = e["emb_slice"]
         # conv outputs that only feed a GroupNorm stay f32 too (one rounding less per branch)
         # every conv whose output feeds a GroupNorm also emits that norm's statistics from its epilogue
-        h, tot = ops.conv3x3(h, e["conv1"], c.emb_bias[lo:hi], c.F, c.H, c.W, stream=True, stats=(c.F, 32))
-        h = self._gn(c, h, e["gn2"], 1e-5, True, True, totals=tot)
+        if m1 is not None:
+            h, tot = ops.conv3x3_mx8(h, m1, c.emb_bias[lo:hi], c.F, c.H, c.W, stats=(c.F, 32))
+        else:
+            h, tot = ops.conv3x3(h, e["conv1"], c.emb_bias[lo:hi], c.F, c.H, c.W, stream=True, stats=(c.F, 32))
+        h = self._gn(c, h, e["gn2"], 1e-5, True, True, totals=tot, mx=m2 is not None)
         # the 1x1 skip conv puts the WHOLE stream through a 16-bit operand: carried as hi + lo (two passes), its
         # rounding was 10 % of the end-to-end error (tests/test_error_budget_gpu.py)
         skip = x if e["skip"] is None else ops.gemm(x, e["skip"][0], e["skip"][1], stream=True, split_a=True)
         if not mod.use_temporal_conv:
-            return self._keep_stats(c, ops.conv3x3(h, e["conv2"][0], e["conv2"][1], c.F, c.H, c.W, residual=skip,
-                                                   stream=True, stats=self._stream_stats(c), out=out))
-        h, tot = ops.conv3x3(h, e["conv2"][0], e["conv2"][1], c.F, c.H, c.W, residual=skip, stream=True,
-                             stats=(c.B, 32))
+            return self._keep_stats(c, conv2(h, residual=skip, stats=self._stream_stats(c), out=out))
+        h, tot = conv2(h, residual=skip, stats=(c.B, 32))
         ident = h
         for i, (gb, wp, b) in enumerate(e["tconv"]):
             lo_h = hi_h = None
+            wmx = mxc["tconv"][i] if mxc is not None else None
             if c.fp is None:
-                t = self._gn(c, h, gb, 1e-5, True, False, totals=tot)
+                t = self._gn(c, h, gb, 1e-5, True, False, totals=tot, mx=wmx is not None)
             else:
                 # frame shards: ONE grouped exchange carries this stage's GroupNorm partial sums and the raw boundary
                 # frames; the halo frames are normalised here, with the same global totals as this rank's own frames
@@ -492,20 +512,25 @@ class UNetModel(packing.PackedWeights, nn.Module):
                 if hi_raw is not None:
                     hi_h = ops.groupnorm(hi_raw, gb[0], gb[1], 1e-5, 1, True, stats_reduce=glob, totals=part)
             if i < 3:
-                h, tot = self._conv_t3(c, t, wp, b, P, halo_lo=lo_h, halo_hi=hi_h, stats=(1, 32))
+                h, tot = self._conv_t3(c, t, wp, b, P, halo_lo=lo_h, halo_hi=hi_h, stats=(1, 32), wmx=wmx)
             else:
                 st = self._stream_stats(c)
                 h = self._keep_stats(c, self._conv_t3(c, t, wp, b, P, residual=ident, halo_lo=lo_h, halo_hi=hi_h,
-                                                      stats=(st[0] // c.B,) + st[1:], out=out))
+                                                      stats=(st[0] // c.B,) + st[1:], out=out, wmx=wmx))
         return h
 
     @staticmethod
-    def _conv_t3(c, t, wp, b, P, residual=None, halo_lo=None, halo_hi=None, stats=None, out=None):
+    def _conv_t3(c, t, wp, b, P, residual=None, halo_lo=None, halo_hi=None, stats=None, out=None, wmx=None):
         """The 3-tap conv over frames of every clip (zero padding at BOTH ends of each clip, openaimodel3d.py:258-269 on
         `(b c t h w)`): the taps must not reach into the neighbouring clip - one clip-aware launch (pm_conv_temporal_k3_clips)
         or, on op tables without it, one launch per clip on its row block.
-        `stats` counts instances PER CLIP; totals of the clips are stacked.  -> (out f32 [F*P, Cout], totals or None)."""
+        `stats` counts instances PER CLIP; totals of the clips are stacked.  -> (out f32 [F*P, Cout], totals or None).
+        `wmx`: the MXFP8 weight pair; then t is the MXFP8 activation pair and the conv runs on pm_conv_temporal_k3_mx8."""
         ops = c.ops
+        if wmx is not None:
+            st = None if stats is None else (stats[0] * c.B,) + tuple(stats[1:])
+            return ops.conv_t3_mx8(t, wmx, b, c.F, P, residual=residual, stats=st, out=out,
+                                   clip_frames=c.T if c.B > 1 else None)
         if c.B == 1:
             return ops.conv_t3(t, wp, b, c.F, P, residual=residual, halo_lo=halo_lo, halo_hi=halo_hi, stream=True,
                                stats=stats, out=out)
