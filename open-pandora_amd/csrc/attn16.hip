@@ -1,5 +1,5 @@
 // Spatial self-attention, head dim 64, on v_mfma_f32_16x16x32 (the other bf16 MFMA shape at the SAME
-// per-wave output tile as attn_self_kernel<T, 1, ...> of attn.hip - 32 query rows x 64 keys per tile and wave - so that
+// per-wave output tile as attn_self_kernel<T, 1, ...> of attn_self.hpp - 32 query rows x 64 keys per tile and wave - so that
 // the two shapes can be ranked by wall time and by the clock the chip holds under each, MI355X_MICROARCH.md "DVFS
 // give-back" item 7 / cdna_hip_programming.md rule 28).  Reference call site: CrossAttention.forward, attention.py:81-144.
 // Measured (profiles/r04/attention_shapes.txt, interleaved, random data, in-kernel clock stamps): this shape holds
@@ -19,7 +19,7 @@
 //                                         - and the V^T fragment uses the same key order: two ds_read_b64_tr_b16 blocks
 //                                         16 keys apart (the MFMA pairs A and B elements by (lane group, element): any
 //                                         contraction order both operands share is legal).
-// LDS images: K rows of 128 B with the 16-byte chunk index XOR-ed with (row >> 1) & 7 (as attn.hip: the ds_read_b128 of
+// LDS images: K rows of 128 B with the 16-byte chunk index XOR-ed with (row >> 1) & 7 (as attn_cross.hpp: the ds_read_b128 of
 // the 16x16x32 A operand - row = lane & 15, chunk = 4 dh + g - is conflict-free on it); V rows of 128 B with the chunk
 // index XOR-ed with ((row >> 1) & 3) << 1: the transposed 4-key x 16-d block reads of a 32-lane half (two blocks stacked
 // in one aligned 8-row group) then touch every bank once (tools/diag/bank_sim.py).
@@ -41,7 +41,7 @@ __device__ __forceinline__ float xor16(float v) { return __shfl_xor(v, 16, 64); 
 // instruction for addresses (the global_load_lds form recomputes clamped 64-bit per-lane addresses: ~23 VALU incl. two
 // v_mul_lo_u32 of the ~127 a tile costs).  A ragged last tile keeps the clamped form.  Measured at N = 9216 (A/B in one
 // process, diagnostics variant 17 = per-lane addresses): -2.5 % cycles per workgroup at the same clock, +1.6 % by wall;
-// the same change in attn_self_kernel (attn.hip): -5.5 % cycles, of which the clock gives most back (1.79 -> 1.69 GHz).
+// the same change in attn_self_kernel (attn_self.hpp): -5.5 % cycles, of which the clock gives most back (1.79 -> 1.69 GHz).
 // MSUM: the softmax denominators come out of the matrix pipe - one more MFMA per (32-key half, query block) whose A operand
 // is a constant all-ones fragment: every row of its 16 x 16 result block is sum_k P^T[k][q], accumulated in f32 over the
 // SAME 16-bit P the numerator uses (a row's weights then sum to one exactly), already replicated over the lanes that need
@@ -64,16 +64,10 @@ __global__ __launch_bounds__(256, 4) void attn_self16_kernel(const AttnParams p)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, g = lane >> 4;
-  int wg = blockIdx.x;
-  {  // XCD-aware: all query tiles of one (frame, head) run on one XCD (its K/V stays in that L2)
-    const int nwg = gridDim.x, qn = nwg >> 3, rn = nwg & 7, xcd = wg & 7;
-    wg = ((xcd < rn) ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (wg >> 3);
-  }
-  const int bh = wg / p.nqt;
-  const int qt = wg - bh * p.nqt;
-  const int b = bh / p.heads, head = bh - b * p.heads;
+  const AttnWork w = attn_work(xcd_workgroup(), p.nqt, p.heads);
+  const int qt = w.qt, b = w.b, head = w.head;
 
-  unsigned long long t_clk0 = 0, t_real0 = 0;
+  unsigned long long t_clk0 = 0, t_real0 = 0;  // (kept per kernel: profiles/attn_split/README.md)
   if constexpr (PM_DIAG_BUILD) {
     if (p.stamps) {
       t_clk0 = __builtin_amdgcn_s_memtime();
@@ -88,20 +82,12 @@ __global__ __launch_bounds__(256, 4) void attn_self16_kernel(const AttnParams p)
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
     qrow[qb] = qt * 128 + wave * 32 + qb * 16 + li;
-    q_valid[qb] = qrow[qb] < p.Nq;
-    if (!q_valid[qb]) qrow[qb] = p.Nq - 1;
+    clamp_qrow(qrow[qb], q_valid[qb], p.Nq);
     const T* qp = reinterpret_cast<const T*>(p.q) + (int64_t)b * p.q_bs + (int64_t)qrow[qb] * p.q_rs + head * 64 + 8 * g;
 #pragma unroll
     for (int dh = 0; dh < 2; ++dh) qf[qb][dh].u = ld_global16(qp + 32 * dh);
   }
-  if (p.prescaled == 0) {  // (uniform) general callers: one extra 16-bit rounding of q * scale * log2(e)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-      for (int dh = 0; dh < 2; ++dh)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qf[qb][dh].e[e] = from_f32<T>(to_f32(qf[qb][dh].e[e]) * p.scale_log2e);
-  }
+  if (p.prescaled == 0) scale_q(qf, p.scale_log2e);  // (uniform)
 
   const int lr = tid >> 3;
   const int Nk = p.Nk[0];
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(256, 4) void attn_self16_kernel(const AttnParams p)
   const int nkt = (Nk + KV_TILE - 1) / KV_TILE;
   const int kc = (tid & 7) ^ ((lr >> 1) & 7);          // source-side swizzles (the DMA writes LDS linearly)
   const int vc = (tid & 7) ^ (((lr >> 1) & 3) << 1);
-  auto load_kv = [&](int kt, int buf) {
+  auto load_kv = [&](int kt, int buf) {  // (kept per kernel: profiles/attn_split/README.md)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       int key = kt * KV_TILE + lr + 32 * j;
@@ -127,7 +113,7 @@ __global__ __launch_bounds__(256, 4) void attn_self16_kernel(const AttnParams p)
   const __amdgpu_buffer_rsrc_t krsrc = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, (short)0, (int)kv_range, 0x00020000);
   const __amdgpu_buffer_rsrc_t vrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, (short)0, (int)kv_range, 0x00020000);
   const uint32_t kvoff = (uint32_t)lr * krs2 + (uint32_t)kc * 16, vvoff = (uint32_t)lr * krs2 + (uint32_t)vc * 16;
-  auto load_kv_full = [&](int kt, int buf) {
+  auto load_kv_full = [&](int kt, int buf) {  // (kept per kernel: profiles/attn_split/README.md)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const uint32_t soff = (uint32_t)(kt * KV_TILE + 32 * j) * krs2;
@@ -303,7 +289,7 @@ __global__ __launch_bounds__(256, 4) void attn_self16_kernel(const AttnParams p)
     }
   };
   load_kv(0, 0);
-  arrive(0);
+  arrive(0);  // (the walk of attn_self_kernel; kept per kernel: profiles/attn_split/README.md)
   tile(0, std::integral_constant<int, 0>{}, std::true_type{});
   int kt = 1;
   // (one tile per trip, stage = kt & 1 at run time: unrolled by two - stages as compile-time constants - hipcc hoists both
@@ -347,29 +333,19 @@ __global__ __launch_bounds__(256, 4) void attn_self16_kernel(const AttnParams p)
   }
 }
 
-
-}  // namespace pm
-
-// launcher used by pm_attention (attn.hip)
-namespace pm {
-int launch_attn_self16(const AttnParams& p, int dtype, dim3 grid, hipStream_t stream, int form) {
-  if constexpr (PM_DIAG_BUILD) {  // (A/B runs: 1 = per-lane addresses of the K/V fetch, 2 = row sums on the vector pipe)
-    if (form == 1) {
-      PM_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((attn_self16_kernel<T, false, true, false>), grid, dim3(256), 0, stream, p);
-                        return check_launch());
-    }
-    if (form == 2) {
-      PM_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((attn_self16_kernel<T, true, false, false>), grid, dim3(256), 0, stream, p);
-                        return check_launch());
-    }
-  }
-  if constexpr (PM_DIAG_BUILD) {
-    if (form == 3) {  // hipcc's own issue order in the PV phase
-      PM_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((attn_self16_kernel<T, true, true, false>), grid, dim3(256), 0, stream, p);
-                        return check_launch());
-    }
-  }
-  PM_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((attn_self16_kernel<T, true, true, true>), grid, dim3(256), 0, stream, p);
+// launcher used by pm_attention (attn.hip).  form 0: the production kernel; diagnostics build only (A/B runs):
+// 1 = per-lane addresses of the K/V fetch, 2 = row sums on the vector pipe, 3 = hipcc's own issue order in the PV phase
+template <bool DESC, bool MSUM, bool PVPIPE>
+static int launch_form(const AttnParams& p, int dtype, dim3 grid, hipStream_t stream) {
+  PM_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((attn_self16_kernel<T, DESC, MSUM, PVPIPE>), grid, dim3(256), 0, stream, p);
                     return check_launch());
+}
+int launch_attn_self16(const AttnParams& p, int dtype, dim3 grid, hipStream_t stream, int form) {
+  if constexpr (PM_DIAG_BUILD) {
+    if (form == 1) return launch_form<false, true, false>(p, dtype, grid, stream);
+    if (form == 2) return launch_form<true, false, false>(p, dtype, grid, stream);
+    if (form == 3) return launch_form<true, true, false>(p, dtype, grid, stream);
+  }
+  return launch_form<true, true, true>(p, dtype, grid, stream);
 }
 }  // namespace pm

@@ -1,5 +1,5 @@
 // The MXFP8 / e4m3 quantisation rule as device code, shared by the MXFP8 GEMM and quantiser (mx8.hip), the fp8 attention's
-// MXFP8 output (attn.hip) and the GroupNorm-apply quantiser (norm.hip).  The rule itself: include/pandora_mi355x.h, "MXFP8"; restated in numpy by tests/test_mx8_cpu.py.
+// MXFP8 output (attn_fp8.hpp) and the GroupNorm-apply quantiser (norm.hip).  The rule itself: include/pandora_mi355x.h, "MXFP8"; restated in numpy by tests/test_mx8_cpu.py.
 #pragma once
 #include "common.hpp"
 

@@ -1,7 +1,10 @@
-"""Exact selection and guard tests of every attention kernel (csrc/attn.hip, csrc/attn16.hip): attn_kernel (two segments, and
+"""Exact selection and guard tests of every attention kernel (csrc/attn_cross.hpp, attn_self.hpp, attn_fp8.hpp, attn_temporal.hpp,
+attn_small.hpp - one unit with the host side, csrc/attn.hip - and csrc/attn16.hip): attn_kernel (two segments, and
 one segment as diagnostics variant 9), attn_self_kernel in its template forms (variants 0 / 1: QB 1, RING 2; 3: QB 2, PIPE,
-RING 4; 5: QB 2, PIPE, POST, RING 4), attn_self16_kernel (by the shipped rule at >= 4096 tokens, forced as variant 16),
-attn_fp8_pack_kernel + attn_fp8_kernel (and the latter alone on the packed operands), tattn_kernel and attn_small_kernel.
+RING 4; 5: QB 2, PIPE, POST, RING 4), attn_self16_kernel (by the shipped rule at >= 4096 tokens, forced as variant 16, and its
+diagnostics forms 17 / 18 / 19: per-lane K/V addresses, row sums on the vector pipe, hipcc's own PV order),
+attn_fp8_pack_kernel + attn_fp8_kernel (and the latter alone on the packed operands; variant 2: 64 rows per wave),
+tattn_kernel and attn_small_kernel.
 
 Every case of oracle/attn_exact.py CASES (the table tests/test_attn_exact_cpu.py proves against an f64 softmax) has a result
 that is exact in f16 and bf16 - ties of 1, 2 or 4 keys placed across the first / fast / ragged tiles and ring stages, every
@@ -24,7 +27,10 @@ GUARD = 24576.0  # around a strided output (exact in f16 and bf16)
 GUARD_ROWS, COL0, COL_TAIL = 3, 64, 8
 SELF_VARIANTS = {0: "attn_self_kernel<QB 1, RING 2> (shipped library)", 1: "attn_self_kernel<QB 1, RING 2> (forced)",
                  3: "attn_self_kernel<QB 2, PIPE, RING 4>", 5: "attn_self_kernel<QB 2, PIPE, POST, RING 4>",
-                 9: "attn_kernel<one segment>", 16: "attn_self16_kernel (forced)"}
+                 9: "attn_kernel<one segment>", 16: "attn_self16_kernel (forced)",
+                 17: "attn_self16_kernel<per-lane K/V addresses>", 18: "attn_self16_kernel<row sums on the vector pipe>",
+                 19: "attn_self16_kernel<hipcc's own PV order>"}
+FP8_VARIANTS = {0: "", 2: " <QB 2: 64 rows per wave>"}
 OTHER_KERNELS = {"cross": "attn_kernel<two segments>", "temporal": "tattn_kernel", "generic": "attn_small_kernel",
                  "fp8": "attn_fp8_pack_kernel + attn_fp8_kernel, and attn_fp8_kernel on the packed operands"}
 
@@ -32,7 +38,10 @@ OTHER_KERNELS = {"cross": "attn_kernel<two segments>", "temporal": "tattn_kernel
 def _params():
     out = []
     for c in ax.CASES:
-        variants = (0,) if c.kind != "self" or c.long else tuple(SELF_VARIANTS)  # (the long case: the shipped rule's own choice)
+        if c.kind == "fp8":
+            variants = tuple(FP8_VARIANTS)
+        else:
+            variants = (0,) if c.kind != "self" or c.long else tuple(SELF_VARIANTS)  # (the long case: the shipped rule's own choice)
         out += [pytest.param(c, v, id=f"{c.id}-v{v}") for v in variants]
     return out
 
@@ -124,7 +133,7 @@ def test_attn_exact(hip_ops_factory, case, variant, dtype):
     ops = hip_ops_factory(dtype) if variant == 0 else hip_ops_factory(dtype, diag=True)
     d = ax.build(case, dtype)
     wanted = ax.want(case, d, dtype)
-    kernel = SELF_VARIANTS[variant] if case.kind == "self" else OTHER_KERNELS[case.kind]
+    kernel = SELF_VARIANTS[variant] if case.kind == "self" else OTHER_KERNELS[case.kind] + FP8_VARIANTS.get(variant, "")
     if case.long:
         assert _shipped_rule_takes_attn16(case), (case.id, "the shipped rule no longer sends this shape to attn_self16_kernel")
         kernel = "attn_self16_kernel (shipped library, Nq and Nk >= 4096)"
