@@ -307,6 +307,27 @@ int pm_attention_generic(const void* q, int64_t q_bs, int64_t q_rs, const void* 
                          int64_t Nq, int64_t D, float scale, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * pm_attention_causal: pm_attention_generic under a causal mask - query row i sees key j iff j <= q_pos0 + i.  For the
+ * OpenCLIP ViT-H/14 text tower of the conditioning tail (condition.py:219-236: `text_transformer_forward` with
+ * `attn_mask=self.model.attn_mask`, 16 heads of 64 channels over 77 tokens).  Same kernel, same limits (D <= 128, D % 8 == 0,
+ * Nk <= 1024) and strides; each query stops scoring, exponentiating and accumulating at its own last visible key.
+ * PM_E_SHAPE for q_pos0 < 0 or q_pos0 + Nq > Nk (so every row sees at least one key).
+ */
+int pm_attention_causal(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v, int64_t k_bs,
+                        int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs, int64_t B, int64_t heads,
+                        int64_t Nq, int64_t D, float scale, int dtype, int64_t q_pos0, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pm_embed_tokens: out[b*N + n, :] = f32(table[ids[b, n], :]) + pos[n, :] - the head of the OpenCLIP text tower
+ * (condition.py:219-236: `token_embedding(text) + positional_embedding`), producing the f32 residual stream.
+ *   ids int64 [B, N] (contiguous); table [V, W] 16-bit (`dtype`), contiguous; pos f32 [N, W], contiguous; out f32 rows of
+ *   stride out_ld (elements, % 4 == 0, >= W); W % 8 == 0; table / pos / out 16-byte aligned.
+ * The kernel clamps each id into [0, V): a bad id reads a valid row, never out of bounds (callers validate ids first).
+ */
+int pm_embed_tokens(const int64_t* ids, const void* table, const float* pos, float* out, int64_t out_ld, int64_t B, int64_t N,
+                    int64_t V, int64_t W, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * MXFP8: OCP e4m3fn elements with one E8M0 (power-of-two) scale per 32 consecutive elements along K, for the projections of
  * BasicTransformerBlock (opt-in, HipOps(fp8_linear=True)) on the block-scaled MFMA v_mfma_scale_f32_16x16x128_f8f6f4 (twice
  * the bf16 rate; the scales are applied inside the instruction).  A quantised [M, K] tensor is an e4m3 byte matrix [M, K]

@@ -67,6 +67,10 @@ SIGNATURES = {
                                         c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "pm_attention_generic": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                      c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p]),
+    "pm_attention_causal": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                    c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_int64, c_void_p]),
+    "pm_embed_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int,
+                                c_void_p]),
     "pm_attention_temporal": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                       c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int,
                                       c_void_p]),

@@ -13,11 +13,16 @@ The reference moves weights around in four shapes:
   * a bare U-Net / AutoencoderKL state_dict (what `UNetModel.state_dict()` returns).
 `split_checkpoint` normalises any of them; `load_unet` / `load_autoencoder` fill the MI355X modules
 (strict: the key sets are identical by construction, tests/test_graph_cpu.py, tests/test_ae_cpu.py).
+`load_text_tower` / `load_image_tower` / `load_resampler` do the same for the three conditioning modules
+(`cond_stage_model.*` -> clip_text, `embedder.*` -> clip_vision, `image_proj_model.*` -> resampler).
 """
 from collections import OrderedDict
 
 UNET_PREFIXES = ("diffusion_model.model.diffusion_model.", "model.diffusion_model.")
 AE_PREFIXES = ("diffusion_model.first_stage_model.", "first_stage_model.")
+TEXT_PREFIXES = ("diffusion_model.cond_stage_model.", "cond_stage_model.")
+IMAGE_PREFIXES = ("diffusion_model.embedder.", "embedder.")
+RESAMPLER_PREFIXES = ("diffusion_model.image_proj_model.", "image_proj_model.")
 
 
 def normalise_keys(obj):
@@ -71,3 +76,34 @@ def load_autoencoder(ae, obj, strict=True):
         raise KeyError("no first-stage weights found (expected keys under first_stage_model.)")
     sd = OrderedDict((k, v) for k, v in parts["first_stage"].items() if not k.startswith("loss."))
     return ae.load_state_dict(sd, strict=strict)
+
+
+def _load_prefixed(module, obj, prefixes, what, strict, bare, keep=None):
+    """Fill `module` from the first prefix of `prefixes` that the checkpoint carries; a checkpoint none of whose keys has
+    any of them but which holds the key `bare` is the module's own state_dict."""
+    full = normalise_keys(obj)
+    sd = _take(full, prefixes)
+    if sd is None and bare in full:
+        sd = full
+    if sd is None:
+        raise KeyError(f"no {what} weights found (expected keys under {prefixes[-1]})")
+    if keep is not None:
+        sd = OrderedDict((k, v) for k, v in sd.items() if keep(k))
+    return module.load_state_dict(sd, strict=strict)
+
+
+def load_text_tower(tower, obj, strict=True):
+    """`cond_stage_model.*` (FrozenOpenCLIPEmbedder: open_clip's text side under `model.`) -> clip_text."""
+    return _load_prefixed(tower, obj, TEXT_PREFIXES, "text-tower", strict, "model.token_embedding.weight")
+
+
+def load_image_tower(tower, obj, strict=True):
+    """`embedder.*` (FrozenOpenCLIPImageEmbedderV2) -> clip_vision.  The reference deletes only `model.transformer` of the CLIP
+    it loads, so a checkpoint still carries the text-side leftovers beside `model.visual.*`; the tower keeps none of them."""
+    return _load_prefixed(tower, obj, IMAGE_PREFIXES, "image-tower", strict, "model.visual.conv1.weight",
+                          keep=lambda k: k.startswith("model.visual."))
+
+
+def load_resampler(resampler, obj, strict=True):
+    """`image_proj_model.*` -> resampler.Resampler."""
+    return _load_prefixed(resampler, obj, RESAMPLER_PREFIXES, "Resampler", strict, "latents")

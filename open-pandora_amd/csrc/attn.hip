@@ -185,21 +185,42 @@ extern "C" int pm_attention_fp8(const void* q, int64_t q_bs, int64_t q_rs, const
   return launch_attn_fp8(p, B, dtype, (hipStream_t)stream);
 }
 
-extern "C" int pm_attention_generic(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v,
-                                    int64_t k_bs, int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs,
-                                    int64_t B, int64_t heads, int64_t Nq, int64_t D, float scale, int dtype,
-                                    void* stream) {
+// pm_attention_generic and pm_attention_causal: one parameter block, one grid, the kernel's CAUSAL flag apart
+static int launch_attn_small(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v, int64_t k_bs,
+                             int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs, int64_t B, int64_t heads,
+                             int64_t Nq, int64_t D, float scale, int dtype, bool causal, int64_t q_pos0, void* stream) {
   if (!q || !k || !v || !o) return PM_E_NULL;
   if (B < 1 || heads < 1 || Nq < 1 || Nk < 1 || Nk > 1024 || D < 8 || D > 128 || (D & 7)) return PM_E_SHAPE;
   if ((q_bs | q_rs | k_bs | k_rs | o_bs | o_rs) & 7) return PM_E_SHAPE;
   if (B * heads > 65535) return PM_E_SHAPE;
+  if (causal && (q_pos0 < 0 || q_pos0 > Nk - Nq)) return PM_E_SHAPE;
   AttnSmallParams p{};
   p.q = q; p.k = k; p.v = v; p.o = o; p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs;
   p.o_bs = o_bs; p.o_rs = o_rs; p.Nq = (int)Nq; p.Nk = (int)Nk; p.heads = (int)heads; p.D = (int)D; p.scale = scale;
+  p.q_pos0 = (int)q_pos0;
   dim3 grid((unsigned)((Nq + 3) / 4), (unsigned)(B * heads));
+  if (causal) {
+    PM_DISPATCH_DTYPE(dtype, T,
+                      hipLaunchKernelGGL((attn_small_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+                      return check_launch());
+  }
   PM_DISPATCH_DTYPE(dtype, T,
-                    hipLaunchKernelGGL((attn_small_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, p);
+                    hipLaunchKernelGGL((attn_small_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
                     return check_launch());
+}
+
+extern "C" int pm_attention_generic(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v,
+                                    int64_t k_bs, int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs,
+                                    int64_t B, int64_t heads, int64_t Nq, int64_t D, float scale, int dtype,
+                                    void* stream) {
+  return launch_attn_small(q, q_bs, q_rs, k, v, k_bs, k_rs, Nk, o, o_bs, o_rs, B, heads, Nq, D, scale, dtype, false, 0, stream);
+}
+
+extern "C" int pm_attention_causal(const void* q, int64_t q_bs, int64_t q_rs, const void* k, const void* v,
+                                   int64_t k_bs, int64_t k_rs, int64_t Nk, void* o, int64_t o_bs, int64_t o_rs,
+                                   int64_t B, int64_t heads, int64_t Nq, int64_t D, float scale, int dtype,
+                                   int64_t q_pos0, void* stream) {
+  return launch_attn_small(q, q_bs, q_rs, k, v, k_bs, k_rs, Nk, o, o_bs, o_rs, B, heads, Nq, D, scale, dtype, true, q_pos0, stream);
 }
 
 extern "C" int pm_attention_temporal(const void* q, int64_t ldq, const void* k, const void* v,

@@ -8,21 +8,27 @@ namespace pm {
 // 80 channels, 32 layers, once per generate call - 5 GFLOP in all): the MFMA kernels (attn_cross / attn_self / attn_fp8.hpp, attn16.hip) are specialised for head
 // dim 64.  One wave per query row: lanes own keys (scores: q from registers, K rows from L2), wave-wide max / sum,
 // probabilities through a 4 KiB LDS row, then lanes own output channels (V rows read coalesced).
+// CAUSAL (pm_attention_causal, the OpenCLIP text tower: condition.py:219-236, 77 tokens, 16 heads of 64 channels): query row i
+// sees keys j <= q_pos0 + i.  The wave's key count shrinks to its own last visible key, so scores, exponentials and the
+// P V loop all stop there (nothing is computed and masked afterwards); with CAUSAL = false nk is p.Nk and the code is the
+// unmasked kernel's, statement for statement.
 struct AttnSmallParams {
   const void *q, *k, *v;
   void* o;
   int64_t q_bs, q_rs, k_bs, k_rs, o_bs, o_rs;
   int Nq, Nk, heads, D;
   float scale;
+  int q_pos0;  // CAUSAL only
 };
 
-template <typename T> __global__ __launch_bounds__(256) void attn_small_kernel(const AttnSmallParams p) {
+template <typename T, bool CAUSAL = false> __global__ __launch_bounds__(256) void attn_small_kernel(const AttnSmallParams p) {
   __shared__ float prob[4][1024];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bh = blockIdx.y, b = bh / p.heads, head = bh - b * p.heads;
   const int qi = blockIdx.x * 4 + wave;
   if (qi >= p.Nq) return;  // (wave-uniform; no block-wide barrier below)
   const int D = p.D, nv = D >> 3;
+  const int nk = CAUSAL ? min(p.Nk, p.q_pos0 + qi + 1) : p.Nk;  // (wave-uniform; >= 1: q_pos0 >= 0)
   const T* qp = reinterpret_cast<const T*>(p.q) + (int64_t)b * p.q_bs + (int64_t)qi * p.q_rs + head * D;
   const T* kb = reinterpret_cast<const T*>(p.k) + (int64_t)b * p.k_bs + head * D;
   const T* vb = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.k_bs + head * D;
@@ -42,7 +48,7 @@ template <typename T> __global__ __launch_bounds__(256) void attn_small_kernel(c
   for (int t = 0; t < 16; ++t) {
     const int j = lane + 64 * t;
     sc[t] = -INFINITY;
-    if (j < p.Nk) {
+    if (j < nk) {
       const T* kr = kb + (int64_t)j * p.k_rs;
       float a = 0.f;
 #pragma unroll
@@ -63,7 +69,7 @@ template <typename T> __global__ __launch_bounds__(256) void attn_small_kernel(c
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
     const int j = lane + 64 * t;
-    if (j < p.Nk) {
+    if (j < nk) {
       const float e = __expf(sc[t] - mx);
       l += e;
       prob[wave][j] = e;
@@ -75,7 +81,7 @@ template <typename T> __global__ __launch_bounds__(256) void attn_small_kernel(c
   // output channels d = lane and lane + 64
   float o0 = 0.f, o1 = 0.f;
   const bool h0 = lane < D, h1 = lane + 64 < D;
-  for (int j = 0; j < p.Nk; ++j) {
+  for (int j = 0; j < nk; ++j) {
     const float pj = prob[wave][j];
     const T* vr = vb + (int64_t)j * p.k_rs;
     if (h0) o0 = fmaf(pj, to_f32(vr[lane]), o0);

@@ -216,6 +216,52 @@ extern "C" int pm_split16(const float* x, int64_t ldx, void* y, int64_t ldy, int
   return pm::check_launch();
 }
 
+// Token-embedding lookup of the OpenCLIP text tower (condition.py:219-236: token_embedding(text) + positional_embedding):
+// out[b*N + n, :] = f32(table[ids[b, n], :]) + pos[n, :].  One thread per 8 channels: one 16-byte table load, two 16-byte
+// pos loads, two 16-byte stores.  The id is clamped into [0, V) here (the host wrapper rejects such ids before the launch),
+// so no id can make the kernel read outside the table.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_tokens_kernel(const long long* __restrict__ ids, const T* __restrict__ table,
+                                                           const float* __restrict__ pos, float* __restrict__ out,
+                                                           int64_t out_ld, int64_t M, int N, int64_t V, int W8) {
+  const int64_t total = M * W8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t m = i / W8;
+    const int c = (int)(i - m * W8) * 8;
+    const int n = (int)(m % N);
+    long long id = ids[m];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    pm::Pack8<T> t;
+    t.u = pm::ld_global16(table + id * ((int64_t)W8 * 8) + c);
+    const float* pp = pos + (int64_t)n * W8 * 8 + c;
+    pm::f32x4 a = *reinterpret_cast<const pm::f32x4*>(pp);
+    pm::f32x4 b = *reinterpret_cast<const pm::f32x4*>(pp + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a[e] += pm::to_f32(t.e[e]);
+      b[e] += pm::to_f32(t.e[e + 4]);
+    }
+    float* op = out + m * out_ld + c;
+    *reinterpret_cast<pm::f32x4*>(op) = a;
+    *reinterpret_cast<pm::f32x4*>(op + 4) = b;
+  }
+}
+
+extern "C" int pm_embed_tokens(const int64_t* ids, const void* table, const float* pos, float* out, int64_t out_ld, int64_t B,
+                               int64_t N, int64_t V, int64_t W, int dtype, void* stream) {
+  if (!ids || !table || !pos || !out) return PM_E_NULL;
+  if (B < 1 || N < 1 || V < 1 || W < 8 || (W & 7) || (out_ld & 3) || out_ld < W || N > (1 << 20) || W > (1 << 20)) return PM_E_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(out)) & 15) return PM_E_SHAPE;
+  const int64_t M = B * N, total = M * (W / 8);
+  int64_t nb = (total + 255) / 256;
+  if (nb > 8192) nb = 8192;
+  PM_DISPATCH_DTYPE(dtype, T,
+                    hipLaunchKernelGGL((embed_tokens_kernel<T>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                                       reinterpret_cast<const long long*>(ids), reinterpret_cast<const T*>(table), pos, out,
+                                       out_ld, M, (int)N, V, (int)(W / 8)));
+  return pm::check_launch();
+}
+
 // The same conversion written through a nearest-neighbour x2 upsample: output pixel (f, oy, ox) of a 2H x 2W frame takes
 // input pixel (f, oy >> 1, ox >> 1).  One thread per 8 elements of an OUTPUT row (each input chunk is read four times: L2).
 template <typename T>

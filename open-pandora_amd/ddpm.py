@@ -7,8 +7,11 @@ Mirrors the inference-relevant surface of lvdm.models.ddpm3d:
   LatentDiffusion.apply_model       ddpm3d.py:724-739
   DiffusionWrapper.forward (hybrid) ddpm3d.py:1066-1081
   predict_{start,eps}_from_z_and_v  ddpm3d.py:235-247
-Losses, logging, EMA, the DDPM ancestral sampler, first-stage and condition encoders are out of scope
-(SURVEY §2.1 rows 2, 8, 9); condition tensors are handed in directly.
+  LatentDiffusion.get_learned_conditioning  ddpm3d.py:573-584 (the text tower's `encode`)
+Losses, logging, EMA and the DDPM ancestral sampler are out of scope.  The first-stage and
+condition encoders are modules of their own (autoencoder / clip_text / clip_vision / resampler); `attach_conditioners`
+hangs them on the shell under the reference's attribute names WITHOUT registering them as submodules, so the shell's
+`state_dict()` stays the schedule tables + the U-Net whether or not anything is attached.
 """
 import numpy as np
 import torch
@@ -77,6 +80,26 @@ class LatentVisualDiffusion(nn.Module):
         # target, no learned log-variance, no ELBO term
         self.loss_type, self.l_simple_weight, self.original_elbo_weight, self.learn_logvar = "l2", 1.0, 0.0, False
         self.logvar = torch.zeros(self.num_timesteps)
+
+    # -- conditioning modules (ddpm3d.py:531-571 instantiate_first_stage / instantiate_cond_stage, :1009-1020) ------------------
+    def attach_conditioners(self, cond_stage_model=None, embedder=None, image_proj_model=None, first_stage_model=None):
+        """Hang the text tower / image tower / Resampler / AutoencoderKL on the shell as plain attributes under the
+        reference's names.  They are NOT registered as submodules: `state_dict()`, `.to()` and `load_state_dict` of the
+        shell see the schedule tables and the U-Net, as before."""
+        given = dict(cond_stage_model=cond_stage_model, embedder=embedder, image_proj_model=image_proj_model,
+                     first_stage_model=first_stage_model)
+        for name, module in given.items():
+            if module is not None:
+                object.__setattr__(self, name, module)  # (nn.Module.__setattr__ would register it)
+        return self
+
+    def get_learned_conditioning(self, c):
+        """ddpm3d.py:573-584: `cond_stage_model.encode(c)` - c a list of prompts (or token ids) -> (b, 77, 1024)."""
+        tower = getattr(self, "cond_stage_model", None)
+        if tower is None:
+            raise RuntimeError("get_learned_conditioning: no cond_stage_model attached "
+                               "(attach_conditioners(cond_stage_model=...), or build the runner with factory.build_runner)")
+        return tower.encode(c)
 
     @property
     def device(self):

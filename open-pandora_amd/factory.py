@@ -1,5 +1,6 @@
 """Model assembly for the two shipped resolutions (DynamiCrafter/configs/inference_{512,1024}_v1.0.yaml
-`model.params`): U-Net hyper-parameters, diffusion shell, op-table binding, seeded synthetic weights."""
+`model.params`): U-Net hyper-parameters, diffusion shell, op-table binding, seeded synthetic weights; and `build_runner`,
+the one call from a shipped yaml plus a checkpoint to a working `wm.DiffusionRunner`."""
 import torch
 import yaml
 
@@ -57,3 +58,44 @@ def build_diffusion(resolution="320x512", ops=None, seed=20230211, unet_override
     if ops is not None:
         unet.bind(ops)
     return LatentVisualDiffusion(unet, **shell, **r)
+
+
+def build_runner(yaml_path, checkpoint, ops, *, decode=True):
+    """yaml + checkpoint -> `wm.DiffusionRunner`: what `instantiate_from_config` + `load_state_dict` + the conditioning calls of
+    `image_guided_synthesis` (model.py:703-729) do in the reference.  Builds the five modules that a DynamiCrafter /
+    Open-Pandora checkpoint carries from the yaml's `model.params` - `unet_config`, `first_stage_config`,
+    `cond_stage_config`, `img_cond_stage_config`, `image_proj_stage_config` - on the meta device, fills each from its prefix
+    of the checkpoint (strict; any of the wire formats of checkpoint.py), binds `ops` and attaches the four conditioning
+    modules to the shell under the reference's names.  The runner embeds images through `wm.ImageContext` (tower ->
+    Resampler) and takes the unconditional text tokens from the text tower, run once on "" when guidance first needs them.
+    `checkpoint`: a path (torch.load, weights only) or an already loaded object.  decode=False: the runner returns latents."""
+    import os
+
+    from . import checkpoint as ckpt, wm
+    from .autoencoder import AutoencoderKL
+    from .clip_text import FrozenOpenCLIPEmbedder
+    from .clip_vision import FrozenOpenCLIPImageEmbedderV2
+    from .resampler import Resampler
+    y = params_from_yaml(yaml_path)
+    missing = [k for k in ("unet_config", "first_stage_config", "cond_stage_config", "img_cond_stage_config",
+                           "image_proj_stage_config") if k not in y]
+    if missing:
+        raise KeyError(f"{yaml_path}: model.params lacks {missing}")
+    if isinstance(checkpoint, (str, os.PathLike)):
+        checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=True)
+    pm = build_diffusion(ops=ops, yaml_path=yaml_path, weights="empty")
+    params = lambda key: dict(y[key].get("params") or {})
+    with torch.device("meta"):
+        ae = AutoencoderKL(**dict(params("first_stage_config"), scale_factor=y.get("scale_factor", 0.18215)))
+        text = FrozenOpenCLIPEmbedder(**params("cond_stage_config"))
+        image = FrozenOpenCLIPImageEmbedderV2(**params("img_cond_stage_config"))
+        proj = Resampler(**params("image_proj_stage_config"))
+    ckpt.load_unet(pm.model.diffusion_model, checkpoint)
+    for module, load in ((ae, ckpt.load_autoencoder), (text, ckpt.load_text_tower), (image, ckpt.load_image_tower),
+                         (proj, ckpt.load_resampler)):
+        module.to_empty(device=ops.device)
+        load(module, checkpoint)
+        module.eval().bind(ops)
+    pm.attach_conditioners(cond_stage_model=text, embedder=image, image_proj_model=proj, first_stage_model=ae)
+    return wm.DiffusionRunner(pm, wm.ImageContext(image, proj), pm.get_learned_conditioning, ae.encode_first_stage,
+                              ae.decode_first_stage if decode else None)

@@ -740,6 +740,38 @@ class HipOps:
         capi.check(rc, f"pm_attention_generic B={B} heads={heads} Nq={Nq} D={D}")
         return out
 
+    def attention_causal(self, q, k, v, heads, q_pos0=0, out=None):
+        """attention_generic under a causal mask (pm_attention_causal): query row i sees keys j <= q_pos0 + i."""
+        B, Nq, C = q.shape
+        D = C // heads
+        assert D * heads == C and q.stride(2) == 1 and k.stride(2) == 1 and k.shape == v.shape and k.stride() == v.stride()
+        if out is None:
+            out = self.empty(B, Nq, C)
+        rc = self.lib.pm_attention_causal(_ptr(q), q.stride(0), q.stride(1), _ptr(k), _ptr(v), k.stride(0), k.stride(1),
+                                          k.shape[1], _ptr(out), out.stride(0), out.stride(1), B, heads, Nq, D,
+                                          float(D) ** -0.5, self.dt, int(q_pos0), self._stream())
+        capi.check(rc, f"pm_attention_causal B={B} heads={heads} Nq={Nq} Nk={k.shape[1]} D={D} q_pos0={q_pos0}")
+        return out
+
+    def embed_tokens(self, ids, table, pos, out=None):
+        """ids int64 [B, N], table [V, W] 16-bit, pos f32 [N, W] -> f32 [B*N, W] = table[ids] + pos (pm_embed_tokens).
+        An id outside [0, V) is a ValueError here, before the launch (the kernel would clamp it)."""
+        B, N = ids.shape
+        V, W = table.shape
+        assert ids.dtype == torch.int64 and table.dtype == self.dtype and table.is_contiguous()
+        assert pos.dtype == torch.float32 and pos.shape == (N, W) and pos.is_contiguous()
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo < 0 or hi >= V:
+            raise ValueError(f"embed_tokens: token ids span [{lo}, {hi}], the table has {V} rows")
+        ids = ids.to(self.device).contiguous()
+        if out is None:
+            out = torch.empty(B * N, W, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.shape == (B * N, W) and out.stride(1) == 1
+        rc = self.lib.pm_embed_tokens(_ptr(ids), _ptr(table), _ptr(pos), _ptr(out), out.stride(0), B, N, V, W, self.dt,
+                                      self._stream())
+        capi.check(rc, f"pm_embed_tokens B={B} N={N} V={V} W={W}")
+        return out
+
     def attention_temporal(self, q, k, v, heads, out=None):
         """q [Fq, P, heads*64], k/v [Fk, P, heads*64] views: attention over frames at each pixel."""
         Fq, P, C = q.shape

@@ -129,10 +129,26 @@ class DiffusionRunner:
     def __init__(self, diffusion_model, embed_image, uncond_text_emb, encode_first_stage, decode_first_stage=None):
         self.diffusion_model = diffusion_model
         self.embed_image = embed_image
-        self.uncond_text_emb = uncond_text_emb
+        self.uncond_text_emb = uncond_text_emb  # tensor, or the text tower: a callable / module run once on [""]
         self.encode_first_stage = encode_first_stage
         self.decode_first_stage = decode_first_stage
         self.sampler = DDIMSampler(diffusion_model)
+
+    @property
+    def uncond_text_emb(self):
+        """(1, 77, 1024) tokens of the empty prompt (model.py:723-725).  Given as a tensor it is returned as is; given as a
+        callable (the text tower, or `diffusion_model.get_learned_conditioning`) it is called once with [""], when guidance
+        first asks for it, and the result is kept: the prompt never changes."""
+        if self._uncond_text_emb is None and self._uncond_text_fn is not None:
+            with torch.no_grad():
+                self._uncond_text_emb = self._uncond_text_fn([""])
+        return self._uncond_text_emb
+
+    @uncond_text_emb.setter
+    def uncond_text_emb(self, value):
+        lazy = callable(value) and not torch.is_tensor(value)
+        self._uncond_text_fn = value if lazy else None
+        self._uncond_text_emb = None if lazy else value
 
     @torch.no_grad()
     def image_guided_synthesis(self, diffusion_conditioning, videos, diffusion_cond_image, noise_shape, n_samples=1,
