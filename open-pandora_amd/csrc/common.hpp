@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include "../../include/pandora_mi355x.h"
 #ifdef PM_DIAG
 #include "../../include/pandora_mi355x_diag.h"
@@ -115,6 +116,50 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ---- host: what every launcher needs of the current device.  The caches are write-once per slot (a race writes the same value
+// twice); a device index outside them is served without a cache - queried / set on every call, never folded onto another slot.
+constexpr int MAX_DEVICES = 64;
+constexpr int MAX_LDS_KERNELS = 96;  // kernel instantiations that ask for more than 64 KiB of dynamic LDS (diagnostics build: ~50)
+
+inline int current_device() {
+  int dev = -1;
+  return hipGetDevice(&dev) == hipSuccess ? dev : -1;
+}
+
+inline int num_cus() {
+  static std::atomic<int> cus[MAX_DEVICES] = {};
+  const int dev = current_device();
+  const bool cached = dev >= 0 && dev < MAX_DEVICES;
+  int n = cached ? cus[dev].load(std::memory_order_relaxed) : 0;
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev < 0 ? 0 : dev) != hipSuccess || n < 1) n = 256;
+    if (cached) cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+// Allow kernel `fn` `bytes` of dynamic LDS on the current device (the attribute is per kernel AND per device; a process may drive
+// several GPUs).  Set once per (kernel, device); a kernel or device the table has no room for gets it set on every call.
+inline void raise_dynamic_lds(const void* fn, int bytes) {
+  struct Slot {
+    std::atomic<const void*> fn;
+    std::atomic<bool> raised[MAX_DEVICES];
+  };
+  static Slot table[MAX_LDS_KERNELS] = {};
+  const int dev = current_device();
+  std::atomic<bool>* raised = nullptr;
+  for (int i = 0; i < MAX_LDS_KERNELS && dev >= 0 && dev < MAX_DEVICES; ++i) {
+    const void* owner = nullptr;  // the first free slot is claimed for `fn`
+    if (table[i].fn.compare_exchange_strong(owner, fn) || owner == fn) {
+      raised = &table[i].raised[dev];
+      break;
+    }
+  }
+  if (raised != nullptr && raised->load(std::memory_order_acquire)) return;
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (raised != nullptr) raised->store(true, std::memory_order_release);
 }
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? PM_OK : PM_E_LAUNCH; }

@@ -1,7 +1,7 @@
 // Host side of the MFMA GEMM family for gfx950: process state, the split-K plan, the ONE kernel choice (choose_kernel),
 // the launchers and the C entry points pm_gemm / pm_conv2d_3x3 / pm_conv_temporal_k3*.  The kernels of this translation
 // unit live in gemm_2stage.hpp (128x128, two LDS stages: any shape), gemm_ring.hpp (128x128 and 256x128 ring kernels)
-// and gemm_splitk_reduce.hpp; gemm256.hip, gemm_wide.hip and gemm_wide_stream.hip are units of their own.
+// and gemm_splitk_reduce.hpp; gemm_wide.hip and gemm_wide_stream.hip are units of their own.
 #include "gemm_common.hpp"
 #include "gemm_2stage.hpp"
 #include "gemm_ring.hpp"
@@ -9,24 +9,16 @@
 
 namespace pm {
 
-// Process-level state of this file, all of it write-once: three environment overrides read by init_once() before
-// their first use (from EVERY entry point that depends on them, so a sizing query and the launch it sizes agree),
-// and per-DEVICE caches (CU count, "dynamic LDS limit raised" per kernel instantiation - the attribute is per
-// device, a process may drive several GPUs).
-constexpr int MAX_DEVICES = 64;
+// Process-level state of this file, all of it write-once: the environment overrides read by init_once() before
+// their first use (from EVERY entry point that depends on them, so a sizing query and the launch it sizes agree).
+// The per-device caches (CU count, dynamic LDS limit) are common.hpp's num_cus() / raise_dynamic_lds().
 static int g_ring = 1;  // PANDORA_GEMM_RING: 0 = never, 1 = by prefer_ring(), 2 = always
 static int g_ringw = 1;  // PANDORA_GEMM_RINGW: 0 = never, 1 = by prefer_ringw(), 2 (with PANDORA_GEMM_RING=2) = every unsplit 16-bit call
-static int g_num_cus[MAX_DEVICES] = {0};
 static int g_natural = 1;          // PANDORA_GEMM_NATURAL (diagnostics build): 0 = interleaved W rows for the f32 flavours too (A/B)
 static int g_split_min_nk = 24;     // PANDORA_SPLITK_MIN_NK: shortest K loop (in 64-wide tiles) that is split
 static int g_split_max_tiles = 384; // PANDORA_SPLITK_MAX_TILES: grids of at least this many tiles never split
 static int g_split_force = 0;       // PANDORA_SPLITK_FORCE = s > 0: every splittable call takes (up to) s slices (sweeps that fit the model)
 
-static int current_device() {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return (dev >= 0 && dev < MAX_DEVICES) ? dev : 0;
-}
 #ifdef PM_RING_PROF
 static long long* g_ring_prof = nullptr;  // RingStamps' destination (tools/ring_prof.py)
 extern "C" void pm_debug_ring_prof(void* buf) { g_ring_prof = reinterpret_cast<long long*>(buf); }
@@ -135,16 +127,6 @@ template <typename T> static void launch_reduce(const GemmParams& p, hipStream_t
   hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, p);
 }
 
-static int num_cus() {
-  const int dev = current_device();
-  if (g_num_cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    g_num_cus[dev] = n;
-  }
-  return g_num_cus[dev];
-}
-
 template <typename T, int AMODE, bool A32> static int launch1(const GemmParams& p, hipStream_t stream) {
   constexpr int lds = 4 * TILE_BYTES;
   GemmParams q = p;
@@ -152,13 +134,7 @@ template <typename T, int AMODE, bool A32> static int launch1(const GemmParams& 
   const int64_t nwork = (int64_t)q.mtiles * p.ntiles * p.splits;
   // one work item per workgroup (persistent 2-stage workgroups measured: 2 per CU = no gain, 1 or 3 per CU 5 % slower)
   const int grid = (int)nwork;
-  static bool attr_set[MAX_DEVICES] = {false};  // per device; idempotent (a benign race sets the same value twice)
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<T, AMODE, A32>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set[dev] = true;
-  }
+  raise_dynamic_lds(reinterpret_cast<const void*>(gemm_kernel<T, AMODE, A32>), lds);
   hipLaunchKernelGGL((gemm_kernel<T, AMODE, A32>), dim3(grid), dim3(256), lds, stream, q);
   if (p.splits > 1) launch_reduce<T>(p, stream);
   return check_launch();
@@ -183,13 +159,7 @@ template <typename T, int AMODE> static int launch_ringw(const GemmParams& p, hi
   q.mtiles = (p.M + 255) / 256;
   const int64_t nwork = (int64_t)q.mtiles * p.ntiles;
   const int grid = (int)(nwork < num_cus() ? nwork : num_cus());
-  static bool attr_set[MAX_DEVICES] = {false};
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ringw_kernel<T, AMODE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, RINGW_LDS);
-    attr_set[dev] = true;
-  }
+  raise_dynamic_lds(reinterpret_cast<const void*>(gemm_ringw_kernel<T, AMODE>), RINGW_LDS);
   hipLaunchKernelGGL((gemm_ringw_kernel<T, AMODE>), dim3(grid), dim3(512), RINGW_LDS, stream, q);
   return check_launch();
 }
@@ -202,13 +172,7 @@ template <typename T, int AMODE> static int launch_ring(const GemmParams& p, hip
   q.mtiles = (p.M + BM - 1) / BM;
   const int64_t nwork = (int64_t)q.mtiles * p.ntiles * p.splits;
   const int grid = (int)(nwork < num_cus() ? nwork : num_cus());
-  static bool attr_set[MAX_DEVICES] = {false};
-  const int dev = current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_kernel<T, AMODE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);
-    attr_set[dev] = true;
-  }
+  raise_dynamic_lds(reinterpret_cast<const void*>(gemm_ring_kernel<T, AMODE>), RING_LDS);
   hipLaunchKernelGGL((gemm_ring_kernel<T, AMODE>), dim3(grid), dim3(512), RING_LDS, stream, q);
   if (p.splits > 1) launch_reduce<T>(p, stream);
   return check_launch();
@@ -234,7 +198,8 @@ static bool prefer_ring(int amode, const GemmParams& p) {
 
 // The kernel families of pm_gemm / the convs.  The values are what pm_gemm_kernel_choice returns (bench.py, ops_hip.py and the tests
 // compare against them).
-enum KernelChoice { K_TWO_STAGE = 0, K_RING = 1, K_GEMM256 = 2, K_RINGW = 3, K_WIDE = 4, K_WIDE_STREAM = 5 };
+// (2 was the retired 256x256 8-phase kernel: reserved, never returned)
+enum KernelChoice { K_TWO_STAGE = 0, K_RING = 1, K_RINGW = 3, K_WIDE = 4, K_WIDE_STREAM = 5 };
 
 // THE dispatch rule: which kernel runs a planned call (p after plan_split) with loader `amode`.  The launches and the
 // pm_gemm_kernel_choice query both go through here.
@@ -249,8 +214,6 @@ static KernelChoice choose_kernel(const GemmParams& p, int flags, int amode) {
   if (amode == A_CONV3X3) return K_TWO_STAGE;  // (general 3x3 mode: K tails / nearest-x2 stay on gemm_kernel)
   const bool force_ringw = g_ringw == 2 && g_ring == 2;  // every unsplit 16-bit call on the 256x128 ring kernel (tools/ring_prof.py --ringw)
   if (p.splits == 1 && (force_ringw || (g_ringw == 1 && g_ring != 0 && prefer_ringw(amode, p)))) return K_RINGW;
-  // large MFMA-bound shapes: 256x256 tiles, 8-phase ping-pong (gemm256.hip) - where the 256x128 ring kernel is not preferred
-  if (dense && !force_ringw && gemm256_wanted(p, flags, num_cus())) return K_GEMM256;
   return (g_ring == 2 || (g_ring == 1 && prefer_ring(amode, p))) ? K_RING : K_TWO_STAGE;
 }
 
@@ -261,9 +224,6 @@ template <typename T, int AMODE> static int launch(const GemmParams& p, int flag
       break;
     case K_WIDE:
       if constexpr (AMODE == A_DENSE) return launch_gemm_wide<T>(p, num_cus(), stream);
-      break;
-    case K_GEMM256:
-      if constexpr (AMODE == A_DENSE) return launch_gemm256<T>(p, num_cus(), stream);
       break;
     case K_RINGW:
       if constexpr (AMODE != A_CONV3X3) return launch_ringw<T, AMODE>(p, stream);

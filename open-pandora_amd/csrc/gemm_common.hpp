@@ -1,4 +1,4 @@
-// Shared by the GEMM-family kernel files (gemm.hip: 128x128 kernels; gemm256.hip: the 256x256 8-phase kernel):
+// Shared by the GEMM-family kernel files (gemm.hip: 128x128 kernels; gemm_wide.hip / gemm_wide_stream.hip: 256x256 tiles):
 // the call parameters, the XCD-aware block remap and the register-direct epilogue (bias / activation / residual /
 // GroupNorm column sums / store, all from the accumulators with 16-byte accesses).
 #pragma once
@@ -55,7 +55,7 @@ constexpr int STAGE_LD = 132;            // f32 staging row stride (floats)
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+__host__ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   // Blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous run of tiles so that
   // neighbouring tiles (same A row panel) share one L2.  Bijective for any nwg.
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
@@ -63,21 +63,53 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + (bid >> 3);
 }
 
-// work item -> (row tile, column tile, K slice) for the 2-stage and the ring kernels.  Supertile order: workgroups that
-// run together on one XCD (a contiguous run of ids) cover GM row tiles x several column tiles, so both the A and the W
-// panels they stream stay in that XCD's 4 MiB L2 (row-major order re-fetched the whole W panel set
-// for every row tile: 9x the algorithmic bytes on the wide GEGLU GEMM, profiles/r01/pmc_traffic.md)
-template <int AMODE, int TILE_ROWS>
-__device__ __forceinline__ void decode_work(const GemmParams& p, int w, int& mt, int& nt, int& split) {
+// THE persistent work walk: the work id that workgroup BID of a grid of G takes in its round `round`, or -1 when it has none in
+// that round (nor in any later one).  Workgroups are dealt round-robin over the 8 XCDs (BID % 8), each with its own L2.  When
+// the grid is a whole number of workgroups per XCD and there is more work than workgroups, XCD x owns the CONTIGUOUS id range
+// [x*per, (x+1)*per) and its G/8 workgroups sweep it in rounds of G/8 consecutive ids: tiles that run together, and the tiles
+// of consecutive rounds, share A / W panels in that L2 (the round-major walk i*G + slot re-read the panels from the fabric:
+// FETCH_SIZE 2.2x the algorithmic bytes on the L0 conv, profiles/r01/pmc_traffic.md).  Otherwise round i takes i*G + slot_id.
+// Stated once AS TEXT: PM_WORK_WALK declares the values that do not depend on the round and the lambda `work_id(round)` in the
+// scope that uses them (the two ring kernels), and work_item() below is the same text as a function (what the host-side test
+// tests/test_gemm_walk_cpu.py runs: every id exactly once, nothing behind a block's first -1).  A function or a struct called
+// from the ring kernels instead moves their SGPR spill counts (profiles/gemm_walk/README.md), so they expand the macro.
+#define PM_WORK_WALK(BID, G, NWORK)                                                                    \
+  const bool xcd_walk = ((G) & 7) == 0 && (NWORK) > (G);                                               \
+  const int per_xcd = ((NWORK) + 7) >> 3, gx = (G) >> 3;                                               \
+  const int slot_id = xcd_remap((BID), (G)); /* (fallback: round i -> work item i * G + slot_id) */    \
+  auto work_id = [&](int round) -> int {     /* -1: no work in that round (nor later) */               \
+    if (!xcd_walk) {                                                                                   \
+      const int w = round * (G) + slot_id;                                                             \
+      return w < (NWORK) ? w : -1;                                                                     \
+    }                                                                                                  \
+    const int xcd = (BID) & 7, local = round * gx + ((BID) >> 3);                                      \
+    const int w = xcd * per_xcd + local;                                                               \
+    return (local < per_xcd && w < (NWORK)) ? w : -1;                                                  \
+  }
+__host__ __device__ inline int work_item(int bid, int G, int nwork, int round) {
+  PM_WORK_WALK(bid, G, nwork);
+  return work_id(round);
+}
+
+// tile id -> (row tile, column tile) in supertile order: workgroups that run together on one XCD (a contiguous run of ids)
+// cover GM row tiles x several column tiles, so both the A and the W panels they stream stay in that XCD's 4 MiB L2
+// (row-major order re-fetched the whole W panel set for every row tile: 9x the algorithmic bytes on the wide GEGLU GEMM,
+// profiles/r01/pmc_traffic.md)
+__host__ __device__ __forceinline__ void decode_tile(int mtiles, int ntiles, int w, int& mt, int& nt) {
   constexpr int GM = 8;
-  split = w % p.splits;
-  const int wg = w / p.splits;
-  const int grp = wg / (GM * p.ntiles);
+  const int grp = w / (GM * ntiles);
   const int first_m = grp * GM;
-  const int gm = (p.mtiles - first_m < GM) ? p.mtiles - first_m : GM;
-  const int rin = wg - grp * GM * p.ntiles;
+  const int gm = (mtiles - first_m < GM) ? mtiles - first_m : GM;
+  const int rin = w - grp * GM * ntiles;
   nt = rin / gm;
   mt = first_m + (rin - nt * gm);
+}
+
+// work item -> (row tile, column tile, K slice) for the 2-stage and the ring kernels
+template <int AMODE, int TILE_ROWS>
+__host__ __device__ __forceinline__ void decode_work(const GemmParams& p, int w, int& mt, int& nt, int& split) {
+  split = w % p.splits;
+  decode_tile(p.mtiles, p.ntiles, w / p.splits, mt, nt);
   if (AMODE == A_CONVT3) {
     // temporal conv: row tile (frame f, pixel block b) reads the same pixel block of frames f-1, f, f+1.
     // Enumerate the row tiles pixel-block-major (consecutive ids = consecutive frames of one block), so the
@@ -342,10 +374,7 @@ __device__ __forceinline__ bool residual_into_acc(const GemmParams& p, f32x4 (&a
 }
 
 // rows m0 + wm*64 + i*16 + fr, columns n0 + wn*64 + ...; sblock = index of this wave's 64-row block in colstats
-// ONLY_FAST: compile the fast flavours alone (the caller guarantees their preconditions: gemm256_wanted).  The generic
-// flavour's exec-masked loads and branches are not only dead weight there: left un-waited on a skipped branch, its bias
-// loads stay "pending" in hipcc's bookkeeping on the K loop's back edge and cost an s_waitcnt vmcnt(0) inside the loop.
-template <typename T, bool FAST = true, bool ONLY_FAST = false>
+template <typename T, bool FAST = true>
 __device__ __forceinline__ void epilogue_regs(const GemmParams& p, f32x4 (&acc)[4][4], const float (&bv)[4][4],
                                               int m0, int n0, int wm, int wn, int fr, int fq, int sblock,
                                               int split, bool res_done = false) {
@@ -361,12 +390,10 @@ __device__ __forceinline__ void epilogue_regs(const GemmParams& p, f32x4 (&acc)[
   T* __restrict__ Cg = reinterpret_cast<T*>(p.C);
   const T* __restrict__ Rg = (partial || p.res32 || res_done) ? nullptr : reinterpret_cast<const T*>(p.R);
   float* __restrict__ Cf = partial ? p.ws + (int64_t)split * p.M * p.N : reinterpret_cast<float*>(p.C);
-  const float* __restrict__ Rf = (partial || !p.res32 || res_done) ? nullptr : reinterpret_cast<const float*>(p.R);  // (see ONLY_FAST)
+  const float* __restrict__ Rf = (partial || !p.res32 || res_done) ? nullptr : reinterpret_cast<const float*>(p.R);
   const bool out32 = partial || p.out32 != 0;
   const int64_t ldc = partial ? p.N : p.ldc;
-  // ONLY_FAST callers (gemm256) also drop the statistics and the f32-residual flavours (their host check): less live state
-  const bool want_stats = !ONLY_FAST && (p.colstats != nullptr) && !partial;
-  if constexpr (ONLY_FAST) Rf = nullptr;
+  const bool want_stats = (p.colstats != nullptr) && !partial;
   // ---- fast flavours (every shape of the U-Net except N % 8 != 0, i.e. the 4-channel output conv) ----
   if (FAST && !geglu && (nout & 7) == 0 && (ldc & 7) == 0 && (p.R == nullptr || (p.ldr & 7) == 0)) {
     // bias and activation in place (one uniform branch per activation, not per element group)
@@ -472,7 +499,6 @@ __device__ __forceinline__ void epilogue_regs(const GemmParams& p, f32x4 (&acc)[
     }
     return;
   }
-  if constexpr (ONLY_FAST) return;
   if (geglu) {
     // value block 2jj, gate block 2jj+1 (weights packed [16 value | 16 gate]): 4 output columns per lane
 #pragma unroll
@@ -743,10 +769,6 @@ __device__ __forceinline__ void epilogue_lean32(const GemmParams& p, f32x4 (&acc
     }
   }
 }
-
-// gemm256.hip: the 256x256 8-phase kernel for large dense shapes
-bool gemm256_wanted(const GemmParams& p, int flags, int num_cus);
-template <typename T> int launch_gemm256(const GemmParams& p, int num_cus, hipStream_t stream);
 
 // gemm_wide.hip: 256x256 tile, four waves of 128x128, assembly main loop (r06)
 bool gemm_wide_wanted(const GemmParams& p, int flags, int num_cus);

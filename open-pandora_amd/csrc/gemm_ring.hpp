@@ -64,23 +64,7 @@ __global__ __launch_bounds__(512, 1) void gemm_ring_kernel(const GemmParams p) {
   const int wave = tid >> 6;
   const int G = gridDim.x;
   const int nwork = p.mtiles * p.ntiles * p.splits;
-  // Work walk.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8), each with its own L2.  When
-  // the grid is a whole number of workgroups per XCD, XCD x owns the CONTIGUOUS id range [x*per, (x+1)*per) and
-  // its G/8 workgroups sweep it in rounds of G/8 consecutive ids: tiles that run together, and the tiles of
-  // consecutive rounds, share A / W panels in that L2 (the round-major walk i*G + slot re-read the panels from
-  // the fabric: FETCH_SIZE 2.2x the algorithmic bytes on the L0 conv, profiles/r01/pmc_traffic.md).
-  const bool xcd_walk = (G & 7) == 0 && nwork > G;
-  const int per_xcd = (nwork + 7) >> 3, gx = G >> 3;
-  const int slot_id = xcd_remap(blockIdx.x, G);  // (fallback: round i -> work item i * G + slot_id)
-  auto work_id = [&](int round) -> int {  // -1: this workgroup has no work in that round (nor later)
-    if (!xcd_walk) {
-      const int w = round * G + slot_id;
-      return w < nwork ? w : -1;
-    }
-    const int xcd = blockIdx.x & 7, local = round * gx + (blockIdx.x >> 3);
-    const int w = xcd * per_xcd + local;
-    return (local < per_xcd && w < nwork) ? w : -1;
-  };
+  PM_WORK_WALK(blockIdx.x, G, nwork);  // work_id(round): the family's work walk (gemm_common.hpp)
   const int nk_all = p.K / BK;
 
   auto decode = [&](int w, int& mt, int& nt, int& split) { decode_work<AMODE, BM>(p, w, mt, nt, split); };  // (gemm_common.hpp)
@@ -411,23 +395,9 @@ __global__ __launch_bounds__(512, 1) void gemm_ringw_kernel(const GemmParams p) 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int G = gridDim.x;
   const int nwork = p.mtiles * p.ntiles * p.splits;
-  // Work walk: gemm_ring_kernel's, see there.  Still one copy per kernel: factored into one struct (grid, work count, the
-  // per-XCD split, operator()(round)) the twelve ring instantiations came out of hipcc with the same registers and scratch
-  // but not the same instructions (code size -30 .. +20 bytes, profiles/gemm_split/README.md), and code that is not
-  // identical has to be timed per instantiation first.  The loader waves below (loader_begin, load_tile, issue) are two
-  // copies for the same reason: sharing them has not been tried against that rule yet.
-  const bool xcd_walk = (G & 7) == 0 && nwork > G;
-  const int per_xcd = (nwork + 7) >> 3, gx = G >> 3;
-  const int slot_id = xcd_remap(blockIdx.x, G);  // (fallback: round i -> work item i * G + slot_id)
-  auto work_id = [&](int round) -> int {  // -1: this workgroup has no work in that round (nor later)
-    if (!xcd_walk) {
-      const int w = round * G + slot_id;
-      return w < nwork ? w : -1;
-    }
-    const int xcd = blockIdx.x & 7, local = round * gx + (blockIdx.x >> 3);
-    const int w = xcd * per_xcd + local;
-    return (local < per_xcd && w < nwork) ? w : -1;
-  };
+  // (the loader waves below - loader_begin, load_tile, issue - are still one copy per ring kernel: sharing them has not been
+  // tried against the adoption rule of profiles/gemm_walk/README.md yet)
+  PM_WORK_WALK(blockIdx.x, G, nwork);  // work_id(round): the family's work walk (gemm_common.hpp)
   const int nk_all = p.K / BK;
 
   auto decode = [&](int w, int& mt, int& nt, int& split) { decode_work<AMODE, BMW>(p, w, mt, nt, split); };  // (gemm_common.hpp)

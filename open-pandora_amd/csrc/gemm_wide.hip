@@ -83,8 +83,7 @@ __global__ __launch_bounds__(256) void gemm_wide_kernel(const GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int G = gridDim.x;
   const int nwork = p.mtiles * p.ntiles;
-  // work walk of the ring kernels (gemm.hip): each XCD sweeps a contiguous id range; ids in supertile order (8 row tiles x all
-  // column tiles), so tiles that run together share A / W panels in one L2
+  // work walk: gemm_common.hpp's PM_WORK_WALK written out (kept per kernel: profiles/gemm_walk/README.md)
   const bool xcd_walk = (G & 7) == 0 && nwork > G;
   const int per_xcd = (nwork + 7) >> 3, gx = G >> 3;
   const int slot_id = xcd_remap(blockIdx.x, G);
@@ -120,13 +119,8 @@ __global__ __launch_bounds__(256) void gemm_wide_kernel(const GemmParams p) {
       w = xcd * per_xcd + local;
       if (local >= per_xcd || w >= nwork) break;
     }
-    constexpr int GM = 8;
-    const int grp = w / (GM * p.ntiles);
-    const int first_m = grp * GM;
-    const int gm = (p.mtiles - first_m < GM) ? p.mtiles - first_m : GM;
-    const int rin = w - grp * GM * p.ntiles;
-    const int nt = rin / gm;
-    const int mt = first_m + (rin - nt * gm);
+    int mt, nt;  // supertile order
+    decode_tile(p.mtiles, p.ntiles, w, mt, nt);
     const int m0 = mt * WIDE_BM, n0 = nt * WIDE_BN;
 
     // (r8 / lc re-defined per tile for the same reason as fr_e / fq_e below: nothing of the per-lane offset arithmetic may be
@@ -248,14 +242,7 @@ bool gemm_wide_wanted(const GemmParams& p, int flags, int num_cus) {
 static int g_wide_variant = 0;  // diagnostics build: which generated loop variant bf16 launches run (tools/gen_wide_loop.py VARIANTS)
 
 template <typename T, int V> static int launch_wide_v(const GemmParams& q, int grid, hipStream_t stream) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 16) ? dev : 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_wide_kernel<T, V>), hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    attr_set[dev] = true;
-  }
+  raise_dynamic_lds(reinterpret_cast<const void*>(gemm_wide_kernel<T, V>), WIDE_LDS);
   hipLaunchKernelGGL((gemm_wide_kernel<T, V>), dim3(grid), dim3(256), WIDE_LDS, stream, q);
   return check_launch();
 }

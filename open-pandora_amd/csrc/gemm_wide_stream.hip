@@ -27,10 +27,11 @@ __global__ __launch_bounds__(256) void gemm_wide_stream_kernel(const GemmParams 
   const int wm = wave >> 1, wn = wave & 1;
   const int G = gridDim.x;
   const int nwork = p.mtiles * p.ntiles;
+  // work walk: gemm_common.hpp's PM_WORK_WALK written out (kept per kernel: profiles/gemm_walk/README.md)
   const bool xcd_walk = (G & 7) == 0 && nwork > G;
   const int per_xcd = (nwork + 7) >> 3, gx = G >> 3;
   const int slot_id = xcd_remap(blockIdx.x, G);
-  // ---- this workgroup's tiles, in the ring kernels' walk (gemm.hip): {A tile offset, W tile offset, C offset of this wave's
+  // ---- this workgroup's tiles, in that walk and the family's supertile order (decode_tile): {A tile offset, W tile offset, C offset of this wave's
   // 128 x 128 block, bias offset of its columns}, bytes, one 16-byte table entry per tile
   u32x4* const table = reinterpret_cast<u32x4*>(smem + 128 * 1024 + wave * 1024);
   int ntl = 0;
@@ -44,13 +45,8 @@ __global__ __launch_bounds__(256) void gemm_wide_stream_kernel(const GemmParams 
       w = xcd * per_xcd + local;
       if (local >= per_xcd || w >= nwork) break;
     }
-    constexpr int GM = 8;
-    const int grp = w / (GM * p.ntiles);
-    const int first_m = grp * GM;
-    const int gm = (p.mtiles - first_m < GM) ? p.mtiles - first_m : GM;
-    const int rin = w - grp * GM * p.ntiles;
-    const int nt = rin / gm;
-    const int mt = first_m + (rin - nt * gm);
+    int mt, nt;
+    decode_tile(p.mtiles, p.ntiles, w, mt, nt);
     const int64_t m0 = (int64_t)mt * 256, n0 = (int64_t)nt * 256;
     u32x4 ent;
     ent[0] = (uint32_t)(m0 * p.lda * 2);
@@ -149,16 +145,8 @@ template <typename T> int launch_gemm_wide_stream(const GemmParams& p, int num_c
   const int64_t nwork = (int64_t)q.mtiles * q.ntiles;
   const int grid = (int)(nwork < num_cus ? nwork : num_cus);
   const bool geglu = p.act == PM_ACT_GEGLU;
-  static bool attr_set[16][2] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev = (dev >= 0 && dev < 16) ? dev : 0;
-  if (!attr_set[dev][geglu]) {
-    const void* fn = geglu ? reinterpret_cast<const void*>(gemm_wide_stream_kernel<T, true>)
-                           : reinterpret_cast<const void*>(gemm_wide_stream_kernel<T, false>);
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS);
-    attr_set[dev][geglu] = true;
-  }
+  raise_dynamic_lds(geglu ? reinterpret_cast<const void*>(gemm_wide_stream_kernel<T, true>)
+                          : reinterpret_cast<const void*>(gemm_wide_stream_kernel<T, false>), WS_LDS);
   if (geglu)
     hipLaunchKernelGGL((gemm_wide_stream_kernel<T, true>), dim3(grid), dim3(256), WS_LDS, stream, q);
   else

@@ -280,21 +280,6 @@ __global__ __launch_bounds__(LN_NW * 64, 2) void ln_gemm_kernel(const LnGemmPara
   }
 }
 
-constexpr int LN_MAX_DEVICES = 64;
-
-static int ln_num_cus() {
-  static int cus[LN_MAX_DEVICES] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= LN_MAX_DEVICES) dev = 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
-
 // panel geometry for a K; 0 rows = shape not served
 static int ln_gemm_rb(int64_t K) { return K == 320 ? 8 : 0; }  // 16-row blocks per panel (80 KiB: two workgroups per CU)
 
@@ -308,7 +293,7 @@ static int ln_choose_nsplit(int64_t M, int64_t N, int64_t K, int act, int* nbw_o
   const int64_t panels = (M + bmp - 1) / bmp;
   const double prologue = 20000.0;
   const double per_block = act == PM_ACT_GEGLU ? 10800.0 : 13000.0;
-  const int64_t cus = ln_num_cus(), slots = 2 * cus;
+  const int64_t cus = num_cus(), slots = 2 * cus;
   double best = 0.0;
   int best_s = 1, best_nbw = (int)nb;
   for (int s = 1; s <= 16 && s <= nb; ++s) {
@@ -330,15 +315,7 @@ static int ln_choose_nsplit(int64_t M, int64_t N, int64_t K, int act, int* nbw_o
 
 template <typename T, int RB, int KT> static int launch_ln_gemm(const LnGemmParams& p, hipStream_t stream) {
   constexpr int lds = KT * RB * 16 * 128;
-  static bool attr_set[LN_MAX_DEVICES] = {false};  // per device; idempotent
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= LN_MAX_DEVICES) dev = 0;
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ln_gemm_kernel<T, RB, KT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set[dev] = true;
-  }
+  raise_dynamic_lds(reinterpret_cast<const void*>(ln_gemm_kernel<T, RB, KT>), lds);
   const int panels = (p.M + RB * 16 - 1) / (RB * 16);
   hipLaunchKernelGGL((ln_gemm_kernel<T, RB, KT>), dim3(panels * p.nsplit), dim3(LN_NW * 64), lds, stream, p);
   return check_launch();

@@ -277,24 +277,43 @@ def test_conv_temporal(hip_ops_factory, dtype, F, P, C, halo):
     assert rel_err(got, want + res.float()) <= TOL[dtype]
 
 
+def _xcd_walk_t():
+    """t x t tiles take the XCD branch of the persistent work walk (work_item, csrc/gemm_common.hpp: more tiles than CUs, the
+    grid a whole number of workgroups per XCD) with a ragged last share: the smallest odd t with t * t > CU count (an odd square
+    is never a multiple of 8).  17 on 256 CUs: 289 tiles, 37 per XCD, 30 for the last.  None when the CU count is no multiple of 8
+    (the walk then never takes that branch)."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if cus % 8:
+        return None
+    t = 1
+    while t * t <= cus or (t * t) % 8 == 0:
+        t += 2
+    return t
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_gemm_wide_256x256_asm_loop(hip_ops_factory, dtype):
     """gemm_wide_kernel (csrc/gemm_wide.hip, r06: 256x256 tile, four waves of 128x128, generated assembly main loop with the
     accumulators fixed in a[0:255]), FORCED on every legal call through the diagnostics build (pm_debug_gemm_wide(2)) and checked
     against the other kernels of pm_gemm on the same inputs: exact-integer products (ragged last row / column tiles, K loops of
-    2, 3 and 21 steps = both exits of the unrolled loop), every epilogue flavour incl. the lean 16-bit one (bias, per-column
+    2, 3 and 21 steps = both exits of the unrolled loop; t x t tiles of _xcd_walk_t, ragged in both directions: the XCD branch of
+    the work walk with a ragged last share - also bit for bit against the same call with the kernel off), every epilogue flavour incl. the lean 16-bit one (bias, per-column
     scale, GEGLU), f32 stream + f32 residual + fused GroupNorm statistics; and the library's own rule picks it for a long-K
     shape (choice of the shipped library: pm_gemm at K = 4096 on 4096 x 4096)."""
     ops = hip_ops_factory(dtype, diag=True)
     g = torch.Generator().manual_seed(5)
+    t = _xcd_walk_t()
     try:
-        for M, N, K in [(777, 1000, 128), (512, 512, 192), (1300, 520, 1344)]:
+        for M, N, K in [(777, 1000, 128), (512, 512, 192), (1300, 520, 1344)] + ([(256 * t - 100, 256 * t - 24, 128)] if t else []):
             a = torch.randint(-3, 4, (M, K), generator=g).to(dtype)
             w = torch.randint(-3, 4, (N, K), generator=g).to(dtype)
             w[:, 1::3] *= 0
             want = (a.float() @ w.float().t()).to(dtype).float()
             ops.lib.pm_debug_gemm_wide(2)
-            assert torch.equal(ops.gemm(a.cuda(), w.cuda()).float().cpu(), want), (M, N, K)
+            got = ops.gemm(a.cuda(), w.cuda())
+            assert torch.equal(got.float().cpu(), want), (M, N, K)
+            ops.lib.pm_debug_gemm_wide(0)
+            assert torch.equal(ops.gemm(a.cuda(), w.cuda()), got), (M, N, K)
         M, N, K = 1024, 768, 1280
         a, w = rnd(M, K, dtype=dtype, seed=1), rnd(N, K, dtype=dtype, scale=K ** -0.5, seed=2)
         bias, res = rnd(N, dtype=torch.float32, seed=3), rnd(M, N, dtype=dtype, seed=4)
@@ -328,12 +347,14 @@ def test_gemm_wide_stream_one_statement_kernel(hip_ops_factory, dtype):
     workgroup - K stream continuous across tiles, bias as the accumulators' initial value, conversion + stores in assembly),
     forced through the diagnostics build on whole-tile shapes: exact-integer products must equal the other kernels BIT FOR BIT
     (K loops of 4, 5, 7 and 20 steps: both parities of the two-buffer loop, tiles per workgroup 1 .. 4: the cross-tile stream with
-    odd K-step counts flips the buffer parity between tiles), + bias and GEGLU against the f32 reference, and the library's own
+    odd K-step counts flips the buffer parity between tiles; t x t tiles of _xcd_walk_t: the XCD branch of the work walk with a
+    ragged last share, the whole product against the CPU's), + bias and GEGLU against the f32 reference, and the library's own
     rule sends the model's GEGLU projections there (pm_gemm_kernel_choice == 5)."""
     ops = hip_ops_factory(dtype, diag=True)
     g = torch.Generator().manual_seed(9)
+    t = _xcd_walk_t()
     try:
-        for M, N, K in [(256, 256, 256), (512, 768, 320), (8192, 8192, 448), (1024, 1024, 1280)]:
+        for M, N, K in [(256, 256, 256), (512, 768, 320), (8192, 8192, 448), (1024, 1024, 1280)] + ([(256 * t, 256 * t, 256)] if t else []):
             a = torch.randint(-3, 4, (M, K), generator=g).to(dtype).cuda()
             w = torch.randint(-3, 4, (N, K), generator=g).to(dtype)
             w[:, 1::3] *= 0
@@ -345,6 +366,8 @@ def test_gemm_wide_stream_one_statement_kernel(hip_ops_factory, dtype):
                 outs.append(ops.gemm(a, w).float())
             assert torch.equal(outs[0], outs[1]), (M, N, K)
             assert torch.equal(outs[1][:64, :64].cpu(), (a[:64].float().cpu() @ w[:64].float().cpu().t()).to(dtype).float())
+            if t and M == 256 * t:
+                assert torch.equal(outs[1].cpu(), (a.float().cpu() @ w.float().cpu().t()).to(dtype).float()), (M, N, K)
         M, N, K = 2048, 1536, 640
         a, w = rnd(M, K, dtype=dtype, seed=1), rnd(N, K, dtype=dtype, scale=K ** -0.5, seed=2)
         bias = rnd(N, dtype=torch.float32, seed=3)
@@ -404,6 +427,34 @@ def test_gemm_ringw_256x128_tiles(hip_ops_factory, dtype):
         got_t = ops.conv_t3(x.cuda(), wp.cuda(), bt.cuda(), F, P, halo_lo=lo.cuda() if halo else None,
                             halo_hi=hi.cuda() if halo else None)
         assert rel_err(got_t, want_t) <= TOL[dtype], halo
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gemm_ring_kernels_xcd_walk_ragged_share(hip_ops_factory, dtype):
+    """The XCD branch of the persistent work walk (work_item, csrc/gemm_common.hpp) with a ragged last share on the two ring
+    kernels: t x t tiles (_xcd_walk_t) with a ragged last row tile, each kernel FORCED through the diagnostics build
+    (pm_debug_gemm_ring; pm_gemm_kernel_choice confirms 1 = gemm_ring_kernel, 3 = gemm_ringw_kernel).  Exact-integer operands:
+    bit for bit the CPU product rounded to the dtype, and bit for bit the same call with the ring kernels switched off."""
+    t = _xcd_walk_t()
+    if t is None:
+        pytest.skip("CU count is no multiple of 8: the walk never takes the XCD branch")
+    ops = hip_ops_factory(dtype, diag=True)
+    g = torch.Generator().manual_seed(13)
+    try:
+        for (ring, ringw), choice, (M, N, K) in (((2, 0), 1, (128 * t - 50, 128 * t, 128)), ((2, 2), 3, (256 * t - 100, 128 * t, 512))):
+            a = torch.randint(-3, 4, (M, K), generator=g).to(dtype)
+            w = torch.randint(-3, 4, (N, K), generator=g).to(dtype)
+            w[:, 1::3] *= 0
+            want = (a.float() @ w.float().t()).to(dtype).float()
+            ops.lib.pm_debug_gemm_ring(ring, ringw, 0)
+            assert ops.lib.pm_gemm_kernel_choice(M, N, K, 0, 0, ops.ws_bytes) == choice
+            got = ops.gemm(a.cuda(), w.cuda())
+            assert torch.equal(got.float().cpu(), want), (M, N, K)
+            ops.lib.pm_debug_gemm_ring(0, 0, 0)
+            assert ops.lib.pm_gemm_kernel_choice(M, N, K, 0, 0, ops.ws_bytes) == 0
+            assert torch.equal(ops.gemm(a.cuda(), w.cuda()), got), (M, N, K)
+    finally:
+        ops.lib.pm_debug_gemm_ring(1, 1, 0)
 
 
 def _geglu_ref(a, w, b):

@@ -6,7 +6,7 @@ of two 64-KiB buffers) and reads fragments with ds_read_b128, double-buffered by
 
     python tools/gen_wide_loop.py > open-pandora_amd/csrc/gemm_wide_loop.inc
 
-The text is ONE inline-asm statement body per (dtype, A mode); hipcc cannot hold this tile (profiles/r03/
+The text is ONE inline-asm statement body per dtype (and diagnostics variant); hipcc cannot hold this tile (profiles/r03/
 negative_result_gemm256w_4waves_128x128_agpr.txt: with all 256 AGPRs taken its accumulators are copied, not updated in place).
 Fixed registers (clobbered by the statement): v64-v127 fragment set 0, v128-v191 fragment set 1 (each: W blocks j at +4j, A blocks
 i at +32+4i), v192-v255 the staging set P (A pieces q = 0..7, W pieces q = 8..15), a0-a255 the accumulators (block (i, j) at
@@ -18,14 +18,17 @@ Waits are placed by a scoreboard: LDS operations retire in order (lgkmcnt, 4 bit
 
 NQ = 16          # staging pieces per wave and K-step (8 A + 8 W), 1 KiB each
 ABUF, WBUF = 32768, 32768
-# timing-only ablations (diagnostics variants; results are wrong by construction): drop the global requests / the LDS
-# staging writes / the barrier / the fragment reads inside the loop; "consume": wait for a staging write to retire before its
-# registers are requested again (the safe form; 0 = trust the in-order issue of ds_write's source read)
-OPT = dict(load=1, write=1, bar=1, read=1, consume=1, stamp=0, vmwait=1, lgkwait=1)
 
 
 class Emit:
-    def __init__(self):
+    """Instruction list + scoreboard.  The keyword options are the timing-only ablations of the diagnostics variants (results
+    are wrong by construction): drop the global requests / the LDS staging writes / the barrier / the fragment reads / the
+    waits inside the loop; "consume": wait for a staging write to retire before its registers are requested again (the safe
+    form; 0 = trust the in-order issue of ds_write's source read, what ships); "stamp": shader clock at the loop's entry."""
+
+    def __init__(self, load=1, write=1, bar=1, read=1, consume=0, stamp=0, vmwait=1, lgkwait=1):
+        self.load, self.write, self.bar, self.read, self.consume, self.stamp = load, write, bar, read, consume, stamp
+        self.vmwait, self.lgkwait = vmwait, lgkwait
         self.out = []
         self.lds = []      # issue-ordered LDS ops since the last lgkmcnt(0): (set of vgprs written, set of vgprs read)
         self.lds_done = 0  # how many of them are known complete
@@ -49,7 +52,7 @@ class Emit:
             return
         n_after = len(self.lds) - 1 - idx
         n = min(n_after, 15)
-        if OPT["lgkwait"] or not self.in_loop:
+        if self.lgkwait or not self.in_loop:
             self.ins(f"s_waitcnt lgkmcnt({n})")
         self.lds_done = len(self.lds) - n
 
@@ -80,7 +83,7 @@ class Emit:
                 if idx >= self.vm_done:
                     n = len(self.vm) - 1 - idx
                     assert n < 64
-                    if OPT["vmwait"] or not self.in_loop:
+                    if self.vmwait or not self.in_loop:
                         self.ins(f"s_waitcnt vmcnt({n})")
                     self.vm_done = idx + 1
                 return
@@ -115,19 +118,15 @@ def acc(i, j):
     return 4 * (8 * i + j)
 
 
-def load_piece(e, q, amode):
-    """global -> P[q] for the K-step whose byte offset is in %[kld] (dense) / whose descriptors are current (conv)"""
-    if OPT["consume"]:
-        e.need_consumed(range(preg(q), preg(q) + 4))
+def load_piece(e, q, tmp=False):
+    """global -> P[q] for the K-step whose byte offset is in %[kld] (tmp: an A piece into tmp_reg(q), request id 16 + q)"""
+    dst = tmp_reg(q) if tmp else preg(q)
+    if e.consume:
+        e.need_consumed(range(dst, dst + 4))
     if q < 8:
-        off = f"%[ao{q}]"
-        if amode != "dense":  # conv: padding rows get offset ~0 -> out of range -> zeros (tools/probes/buffer_lds_oob.hip)
-            e.ins(f"v_bfe_i32 %[tmp], %[inv{q}], %[tap], 1")
-            e.ins(f"v_or_b32 %[tmp], %[tmp], %[ao{q}]")
-            off = "%[tmp]"
-        e.vm_load(f"buffer_load_dwordx4 {vr(preg(q))}, {off}, %[adesc], %[kld] offen", q)
+        e.vm_load(f"buffer_load_dwordx4 {vr(dst)}, %[ao{q}], %[adesc], %[kld] offen", 16 + q if tmp else q)
     else:
-        e.vm_load(f"buffer_load_dwordx4 {vr(preg(q))}, %[bo{q - 8}], %[wdesc], %[kld] offen", q)
+        e.vm_load(f"buffer_load_dwordx4 {vr(dst)}, %[bo{q - 8}], %[wdesc], %[kld] offen", q)
 
 
 def write_piece(e, q, buf):
@@ -153,7 +152,16 @@ def tmp_reg(q):
     return 128 + 4 * q  # prologue only: the A pieces of K-step 1 wait in fragment set 1's registers
 
 
-def step_body(e, buf, mfma, amode, sched):
+def hook(hooks, name, e):
+    if name in hooks:
+        hooks[name](e)
+
+
+SCHEDULE_B = ["r"] * 16 + ["w", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "l"]
+BARRIER_SLOT = 62
+
+
+def step_body(e, buf, mfma, load_piece, hooks):
     """One K-step on LDS buffer `buf`: 128 MFMAs, one filler (fragment read / staging write / global request) behind every
     second MFMA: a 16-cycle v_mfma_f32_16x16x32 holds the SIMD's issue for 8 cycles, so one 13-24-cycle filler per MFMA
     stretches every gap (the first schedule: 32 reads cost 17 %, 16 writes 10 %, 16 requests 14 % of the MFMA-only loop,
@@ -161,111 +169,113 @@ def step_body(e, buf, mfma, amode, sched):
     first half : fragment set 1 (this buffer, k-substep 1);  W pieces of K-step +1 -> other buffer, re-requested for +2;  barrier
     second half: fragment set 0 of K-step +1 (other buffer);  A pieces of K-step +2 -> THIS buffer (free behind the barrier),
                  re-requested for +3.
-    `sched` = (pattern of the four filler positions of a group, barrier slot)"""
-    pattern, bar_at = sched
+    Schedule "B": per half the 16 reads first, then the write / request pairs (a request two fillers behind its write): ONE
+    lgkmcnt wait covers a fragment set (the waits are instructions too: ~4 issue cycles each, 48 of them per K-step in an
+    interleaved form).  `load_piece(e, q)` requests staging piece q.  Hook points (name -> callable(e), all optional), where the
+    generators put their K-offset arithmetic: "first_half" in front of MFMA 0, "second_half" in front of MFMA 64 (behind the
+    first half's requests), "end" behind the last MFMA."""
     fill = {}
-    cover = pattern in ("B", "C", "D")
-    if pattern == "B":
-        # reads first, then the write / request pairs (a request two fillers behind its write): ONE lgkmcnt wait covers a
-        # fragment set (the waits are instructions too: ~4 issue cycles each, 48 of them per K-step in the interleaved form)
-        seqs = [["r"] * 16 + ["w", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "l"]] * 2
-    elif pattern in ("C", "D"):
-        # every LDS operation of the first half well ahead of the barrier's lgkmcnt(0) (the requests, which are not LDS
-        # operations, fill the slots in front of it): a drain right behind a ds_write waits out the write's latency
-        seqs = [["r", "r", "w"] * 8 + ["l"] * 8, ["r"] * 16 + ["w"] * 8 + ["l"] * 8]
-    else:
-        seqs = [[pattern[pidx % len(pattern)] for pidx in range(32)]] * 2
     for half in (0, 1):
         nr = nw = nl = 0
-        for pidx in range(32):
-            slot = 64 * half + 2 * pidx + 1
-            kind = seqs[half][pidx]
+        for pidx, kind in enumerate(SCHEDULE_B):
+            f = fill.setdefault(64 * half + 2 * pidx + 1, [])
             if kind == "r":
                 k, idx = FRAG_ORDER[nr]
-                fill.setdefault(slot, []).append(("rd", 1 - half, k, idx, buf if half == 0 else buf ^ 1))
+                f.append(("rd", 1 - half, k, idx, buf if half == 0 else buf ^ 1))
                 nr += 1
             elif kind == "w":
-                if nw == 0 and cover:
-                    fill.setdefault(slot, []).append(("covervm", (8 if half == 0 else 0) + 7))
-                fill.setdefault(slot, []).append(("wr", (8 if half == 0 else 0) + nw, buf ^ 1 if half == 0 else buf))
+                if nw == 0:
+                    f.append(("covervm", (8 if half == 0 else 0) + 7))
+                f.append(("wr", (8 if half == 0 else 0) + nw, buf ^ 1 if half == 0 else buf))
                 nw += 1
-            elif kind == "l":
-                fill.setdefault(slot, []).append(("ld", (8 if half == 0 else 0) + nl))
+            else:
+                f.append(("ld", (8 if half == 0 else 0) + nl))
                 nl += 1
         assert (nr, nw, nl) == (16, 8, 8), (nr, nw, nl)
-    if cover and pattern != "D":
-        fill.setdefault(0, []).append(("cover", 0))
-    fill.setdefault(bar_at, []).append(("bar",))
-    fill.setdefault(64, []).append(("adv",))
+    fill[0] = [("hook", "first_half"), ("cover",)]
+    fill[BARRIER_SLOT] = [("bar",)]
+    fill[64] = [("hook", "second_half")]
     for m in range(128):
         for f in fill.get(m, []):
             if f[0] == "rd":
-                if OPT["read"]:
+                if e.read:
                     read_frag(e, f[1], f[2], f[3], f[4])
             elif f[0] == "wr":
-                if OPT["write"]:
-                    if OPT["load"]:
+                if e.write:
+                    if e.load:
                         e.need_loaded(f[1])
                     write_piece(e, f[1], f[2])
             elif f[0] == "ld":
-                if OPT["load"]:
-                    load_piece(e, f[1], amode)
+                if e.load:
+                    load_piece(e, f[1])
             elif f[0] == "bar":
                 e.drain_lds()
-                if OPT["bar"]:
+                if e.bar:
                     e.ins("s_barrier")
-            elif f[0] == "adv":
-                advance_k(e, amode)
+            elif f[0] == "hook":
+                hook(hooks, f[1], e)
             elif f[0] == "cover":
-                if OPT["read"]:
-                    e.need_written(range(64 + 64 * f[1], 128 + 64 * f[1]))
+                if e.read:
+                    e.need_written(range(64, 128))
             elif f[0] == "covervm":
-                if OPT["load"] and OPT["write"]:
+                if e.load and e.write:
                     e.need_loaded(f[1])
         s, idx = divmod(m, 64)
         i, j = divmod(idx, 8)
         e.need_written(list(range(frag_w(s, j), frag_w(s, j) + 4)) + list(range(frag_a(s, i), frag_a(s, i) + 4)))
         c = acc(i, j)
         e.ins(f"{mfma} a[{c}:{c + 3}], {vr(frag_w(s, j))}, {vr(frag_a(s, i))}, a[{c}:{c + 3}]")
+    hook(hooks, "end", e)
 
 
-def advance_k(e, amode):
-    """K offset of the next requests (clamped to the last K-step: the requests past the end re-read it, harmlessly)"""
-    if amode == "dense":
-        e.ins("s_add_u32 %[kld], %[kld], 128")
-        e.ins("s_min_u32 %[kld], %[kld], %[kmax]")
-    else:
-        raise NotImplementedError(amode)
-
-
-def kernel_text(mfma, amode, sched):
-    e = Emit()
-    # ---- prologue.  State the loop expects at K-step 0: buffer 0 whole; the A half of buffer 1 (K-step 1); P[0..7] requested
-    # for K-step 2 (A), P[8..15] for K-step 1 (W); fragment set 0 read; %[kld] = offset of K-step 2.
+def prologue_staging(e, load_piece, hooks):
+    """The staging state a first K-step expects: buffer 0 whole; the A half of buffer 1 (K-step 1); P[0..7] requested for
+    K-step 2 (A), P[8..15] for K-step 1 (W); fragment set 0 read.  `load_piece(e, q, tmp=True)` requests A piece q into
+    tmp_reg(q) as request 16 + q.  Hook points, where the generators move their K offsets and set the accumulators up:
+    "k1_a" / "k1_w" / "k2_a" in front of the requests of those K-steps, "acc" while K-steps 0 and 1 are in flight, "acc_ready"
+    in front of the barrier."""
     for q in range(NQ):
-        load_piece(e, q, amode)                                      # K-step 0 -> P
-    advance_k(e, amode)
+        load_piece(e, q)                                             # K-step 0 -> P
+    hook(hooks, "k1_a", e)
     for q in range(8):                                               # K-step 1, A pieces -> fragment set 1's registers
-        e.vm_load(f"buffer_load_dwordx4 {vr(tmp_reg(q))}, %[ao{q}], %[adesc], %[kld] offen", 16 + q)
-    for r in range(256):
-        e.ins(f"v_accvgpr_write_b32 a{r}, 0")
+        load_piece(e, q, tmp=True)
+    hook(hooks, "acc", e)
     for q in range(NQ):
         e.need_loaded(q)
         write_piece(e, q, 0)
+    hook(hooks, "k1_w", e)
     for q in range(8, NQ):
-        load_piece(e, q, amode)                                      # K-step 1, W pieces -> P[8..15]
+        load_piece(e, q)                                             # K-step 1, W pieces -> P[8..15]
     for q in range(8):
         e.need_loaded(16 + q)
         e.lds_op(f"ds_write_b128 %[lwa], {vr(tmp_reg(q))} offset:{ABUF + q * 4096}", reads=range(tmp_reg(q), tmp_reg(q) + 4))
-    advance_k(e, amode)
+    hook(hooks, "k2_a", e)
     for q in range(8):
-        load_piece(e, q, amode)                                      # K-step 2, A pieces -> P[0..7]
+        load_piece(e, q)                                             # K-step 2, A pieces -> P[0..7]
+    hook(hooks, "acc_ready", e)
     e.drain_lds()
     e.ins("s_barrier")
     for kind, idx in FRAG_ORDER:
         read_frag(e, 0, kind, idx, 0)
     e.drain_lds()
-    if OPT["stamp"]:  # diagnostics: shader clock at the loop's entry (tools/wide_probe.py --stamps)
+
+
+def advance_k(e):
+    """K offset of the next requests (clamped to the last K-step: the requests past the end re-read it, harmlessly)"""
+    e.ins("s_add_u32 %[kld], %[kld], 128")
+    e.ins("s_min_u32 %[kld], %[kld], %[kmax]")
+
+
+def zero_acc(e):
+    for r in range(256):
+        e.ins(f"v_accvgpr_write_b32 a{r}, 0")
+
+
+def kernel_text(mfma, **options):
+    e = Emit(**options)
+    # ---- prologue; %[kld] = offset of K-step 2 behind it
+    prologue_staging(e, load_piece, {"k1_a": advance_k, "acc": zero_acc, "k2_a": advance_k})
+    if e.stamp:  # diagnostics: shader clock at the loop's entry (tools/wide_probe.py --stamps)
         e.ins("s_memtime %[tpro]")
         e.ins("s_waitcnt lgkmcnt(0)")
     pro = e.out
@@ -276,7 +286,7 @@ def kernel_text(mfma, amode, sched):
         pair = []
         for buf in (0, 1):
             e.out = []
-            step_body(e, buf, mfma, amode, sched)
+            step_body(e, buf, mfma, load_piece, {"second_half": advance_k})
             pair.append(e.out)
         bodies.append(pair)
     assert bodies[1] == bodies[2], "scoreboard did not reach a fixed point"
@@ -314,27 +324,21 @@ def clobbers():
     return f"#define PM_WIDE_CLOBBERS {v},{a},\"memory\",\"scc\"\n"
 
 
-VARIANTS = [  # (tag, schedule, options); V0 ships, the others exist in the diagnostics build only (tools/wide_probe.py --variants)
-    ("V0", ("B", 62), dict(consume=0)),
-    ("V1", ("B", 62), dict(consume=1)),
-    ("V3", ("B", 62), dict(consume=0, load=0)),
-    ("V4", ("B", 62), dict(consume=0, load=0, write=0)),
-    ("V6", ("B", 62), dict(consume=0, load=0, write=0, bar=0, read=0)),
-    ("V7", ("B", 62), dict(consume=0, stamp=1)),
+VARIANTS = [  # (tag, Emit options); V0 ships, the others exist in the diagnostics build only (tools/wide_probe.py --variants)
+    ("V0", dict()),
+    ("V1", dict(consume=1)),
+    ("V3", dict(load=0)),
+    ("V4", dict(load=0, write=0)),
+    ("V6", dict(load=0, write=0, bar=0, read=0)),
+    ("V7", dict(stamp=1)),
 ]
 
 if __name__ == "__main__":
-    # schedule = (set-1 reads from MFMA slot, first ds_write slot, slots between writes, request lag behind its write, barrier
-    #             slot, set-0 reads of the next step from slot 64 + ..)
     print("// GENERATED by tools/gen_wide_loop.py - do not edit")
     print(clobbers())
-    base = dict(OPT)
     for tag, mf in (("BF16", "v_mfma_f32_16x16x32_bf16"), ("F16", "v_mfma_f32_16x16x32_f16")):
-        for vt, sched, opt in VARIANTS:
+        for vt, options in VARIANTS:
             if vt != "V0" and tag != "BF16":
                 continue
-            OPT.update(base)
-            OPT.update(opt)
-            print(c_string(f"PM_WIDE_LOOP_DENSE_{tag}_{vt}", kernel_text(mf, "dense", sched)))
+            print(c_string(f"PM_WIDE_LOOP_DENSE_{tag}_{vt}", kernel_text(mf, **options)))
             print()
-    OPT.update(base)

@@ -14,13 +14,13 @@ whole 256 x 256 tiles only (M % 256 == 0, N % 256 == 0), K >= 256.
 
 Registers (all clobbered): v48-v55 A row offsets, v56-v63 W row offsets (per tile: lane base + tile offset + j x stride),
 v64-v127 / v128-v191 fragment sets 0 / 1 (the epilogue uses set 1: v128-v159 conversion temporaries, v160-v191 the next tile's
-bias), v192-v255 staging set P, a0-a255 accumulators, s90-s99 scalars.  v0-v47 stay the compiler's.  One K-step = the schedule
-"B" of gen_wide_loop.py.  K-step s of a tile: first half stages W(s+1) and requests W(s+2), second half stages A(s+2) and requests
+bias), v192-v255 staging set P, a0-a255 accumulators, s90-s99 scalars.  v0-v47 stay the compiler's.  One K-step = step_body of
+gen_wide_loop.py (as the prologue's staging sequence is its prologue_staging): this file hangs its K-offset walks on their hook
+points and adds the tile table, the bias as the accumulators' initial value, the epilogues and the tile-boundary control flow.
+K-step s of a tile: first half stages W(s+1) and requests W(s+2), second half stages A(s+2) and requests
 A(s+3); steps nk-3 / nk-2 / nk-1 switch the A (second half of nk-3) and W (first half of nk-2) offsets to the next tile."""
-import sys
-
-sys.path.insert(0, __import__("os").path.dirname(__file__))
-from gen_wide_loop import ABUF, WBUF, FRAG_ORDER, NQ, Emit, acc, c_string, frag_a, frag_w, preg, read_frag, vr, write_piece  # noqa: E402
+from gen_wide_loop import Emit, acc, c_string, preg, prologue_staging, tmp_reg, vr
+from gen_wide_loop import step_body as loop_step_body
 
 AO, BO = 48, 56          # v48.. A row offsets, v56.. W row offsets
 T0, BIAS = 128, 160      # epilogue temporaries / next tile's bias (fragment set 1)
@@ -36,11 +36,13 @@ class E2(Emit):
         self.vm.append(-1)
 
 
-def load_piece(e, q):
+def load_piece(e, q, tmp=False):
+    """global -> P[q] (tmp: an A piece into tmp_reg(q), request id 16 + q) for the K-step whose byte offset is in KA / KW"""
+    dst = tmp_reg(q) if tmp else preg(q)
     if q < 8:
-        e.vm_load(f"buffer_load_dwordx4 {vr(preg(q))}, v{AO + q}, %[adesc], {KA} offen", q)
+        e.vm_load(f"buffer_load_dwordx4 {vr(dst)}, v{AO + q}, %[adesc], {KA} offen", 16 + q if tmp else q)
     else:
-        e.vm_load(f"buffer_load_dwordx4 {vr(preg(q))}, v{BO + q - 8}, %[wdesc], {KW} offen", q)
+        e.vm_load(f"buffer_load_dwordx4 {vr(dst)}, v{BO + q - 8}, %[wdesc], {KW} offen", q)
 
 
 def set_a_offsets(e, t):
@@ -61,68 +63,26 @@ def set_w_offsets(e, t):
             e.ins(f"s_add_u32 {STMP}, {STMP}, %[sw]")
 
 
+def set_k(reg, value):
+    return lambda e: e.ins(f"s_mov_b32 {reg}, {value}")
+
+
 def step_body(e, buf, mfma, kind):
-    """kind: 'M' steady, 'T3' / 'T2' / 'T1' the last three K-steps of a tile (offset switches), schedule B of gen_wide_loop"""
-    seq = ["r"] * 16 + ["w", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "w", "l", "l"]
-    fill = {}
-    for half in (0, 1):
-        nr = nw = nl = 0
-        for pidx in range(32):
-            slot = 64 * half + 2 * pidx + 1
-            k = seq[pidx]
-            if k == "r":
-                kk, idx = FRAG_ORDER[nr]
-                fill.setdefault(slot, []).append(("rd", 1 - half, kk, idx, buf if half == 0 else buf ^ 1))
-                nr += 1
-            elif k == "w":
-                if nw == 0:
-                    fill.setdefault(slot, []).append(("covervm", (8 if half == 0 else 0) + 7))
-                fill.setdefault(slot, []).append(("wr", (8 if half == 0 else 0) + nw, buf ^ 1 if half == 0 else buf))
-                nw += 1
-            else:
-                fill.setdefault(slot, []).append(("ld", (8 if half == 0 else 0) + nl))
-                nl += 1
-    fill.setdefault(0, []).append(("cover", 0))
-    fill.setdefault(62, []).append(("bar",))
-    # K offsets: the W requests of the first half advance KW behind them, the A requests of the second half KA
-    fill.setdefault(64, []).append(("advw",))
-    fill.setdefault(127, []).append(("adva",))
-    if kind == "T3":   # second half requests A(next tile, K-step 0)
-        fill.setdefault(64, []).append(("swa",))
-    if kind == "T2":   # first half requests W(next tile, K-step 0)
-        fill.setdefault(0, []).insert(0, ("sww",))
-    for m in range(128):
-        for f in fill.get(m, []):
-            if f[0] == "rd":
-                read_frag(e, f[1], f[2], f[3], f[4])
-            elif f[0] == "wr":
-                e.need_loaded(f[1])
-                write_piece(e, f[1], f[2])
-            elif f[0] == "ld":
-                load_piece(e, f[1])
-            elif f[0] == "bar":
-                e.drain_lds()
-                e.ins("s_barrier")
-            elif f[0] == "advw":
-                e.ins(f"s_add_u32 {KW}, {KW}, 128")
-            elif f[0] == "adva":
-                pass  # (emitted behind the step's last MFMA, below)
-            elif f[0] == "cover":
-                e.need_written(range(64, 128))
-            elif f[0] == "covervm":
-                e.need_loaded(f[1])
-            elif f[0] == "swa":
-                set_a_offsets(e, TAN)
-                e.ins(f"s_mov_b32 {KA}, 0")
-            elif f[0] == "sww":
-                set_w_offsets(e, TWN)
-                e.ins(f"s_mov_b32 {KW}, 0")
-        s, idx = divmod(m, 64)
-        i, j = divmod(idx, 8)
-        e.need_written(list(range(frag_w(s, j), frag_w(s, j) + 4)) + list(range(frag_a(s, i), frag_a(s, i) + 4)))
-        c = acc(i, j)
-        e.ins(f"{mfma} a[{c}:{c + 3}], {vr(frag_w(s, j))}, {vr(frag_a(s, i))}, a[{c}:{c + 3}]")
-    e.ins(f"s_add_u32 {KA}, {KA}, 128")
+    """kind: 'M' steady, 'T3' / 'T2' / 'T1' the last three K-steps of a tile (offset switches).  K offsets: the W requests of the
+    first half advance KW behind them, the A requests of the second half KA."""
+    def first_half(e):
+        if kind == "T2":   # first half requests W(next tile, K-step 0)
+            set_w_offsets(e, TWN)
+            e.ins(f"s_mov_b32 {KW}, 0")
+
+    def second_half(e):
+        e.ins(f"s_add_u32 {KW}, {KW}, 128")
+        if kind == "T3":   # second half requests A(next tile, K-step 0)
+            set_a_offsets(e, TAN)
+            e.ins(f"s_mov_b32 {KA}, 0")
+
+    loop_step_body(e, buf, mfma, load_piece,
+                   {"first_half": first_half, "second_half": second_half, "end": lambda e: e.ins(f"s_add_u32 {KA}, {KA}, 128")})
 
 
 def bias_loads(e, tb, geglu):
@@ -271,35 +231,16 @@ def prologue(e, geglu):
     set_w_offsets(e, TW)
     e.ins(f"s_mov_b32 {KA}, 0")
     e.ins(f"s_mov_b32 {KW}, 0")
-    for q in range(NQ):
-        load_piece(e, q)                                          # K-step 0 -> P
-    e.ins(f"s_mov_b32 {KA}, 128")
-    for q in range(8):                                            # K-step 1, A pieces -> fragment set 1's registers v128..v159
-        e.vm_load(f"buffer_load_dwordx4 {vr(128 + 4 * q)}, v{AO + q}, %[adesc], {KA} offen", 16 + q)
-    bias_loads(e, TB, geglu)
-    for q in range(NQ):
-        e.need_loaded(q)
-        write_piece(e, q, 0)
-    e.ins(f"s_mov_b32 {KW}, 128")
-    for q in range(8, NQ):
-        load_piece(e, q)                                          # K-step 1, W pieces -> P[8..15]
-    for q in range(8):
-        e.need_loaded(16 + q)
-        e.lds_op(f"ds_write_b128 %[lwa], {vr(128 + 4 * q)} offset:{ABUF + q * 4096}", reads=range(128 + 4 * q, 132 + 4 * q))
-    e.ins(f"s_mov_b32 {KA}, 256")
-    for q in range(8):
-        load_piece(e, q)                                          # K-step 2, A pieces -> P[0..7]
-    acc_init(e, geglu)
-    e.drain_lds()
-    e.ins("s_barrier")
-    for kind, idx in FRAG_ORDER:
-        read_frag(e, 0, kind, idx, 0)
-    e.drain_lds()
+
+    def acc_requests(e):
+        bias_loads(e, TB, geglu)
+
+    prologue_staging(e, load_piece, {"k1_a": set_k(KA, 128), "acc": acc_requests, "k1_w": set_k(KW, 128), "k2_a": set_k(KA, 256),
+                                     "acc_ready": lambda e: acc_init(e, geglu)})
 
 
 def build(mfma, geglu, cvt):
-    e = E2()
-    e.in_loop = False
+    e = E2()  # (no ablation: Emit's options at their shipped values)
     prologue(e, geglu)
     tile_start(e)
     pro = e.out

@@ -19,7 +19,6 @@ if "--build" in sys.argv or "--rebuild" in sys.argv or not os.path.exists(LIB):
         sys.exit(0)
 os.environ["PANDORA_LIB"] = LIB
 os.environ["PANDORA_GEMM_RING"] = "2"
-os.environ["PANDORA_GEMM256"] = "0"
 if "--ringw" in sys.argv:
     os.environ["PANDORA_GEMM_RINGW"] = "2"
 import torch  # noqa: E402
