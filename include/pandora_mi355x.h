@@ -468,6 +468,21 @@ int pm_ddim_update(const float* x, const void* e_c, const void* e_u, const float
                    int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * pm_q_sample: forward noising of B clips, each to its own table index:
+ *   out[b, i] = tab_a[t[b]] * x0[b, i] + tab_b[t[b]] * noise[b, i],   b < B, i < n.
+ * replaces DDIMSampler.stochastic_encode (ddim.py:314-328: extract_into_tensor per batch element, two products, one sum) -
+ * the same expression as q_sample (ddpm3d.py:301-304).  Each product and the sum are rounded to f32 separately (no FMA
+ * contraction): the result equals `a.view(B, 1, ...) * x0 + s.view(B, 1, ...) * noise` in torch bit for bit.
+ *   x0, noise, out f32 [B, n], contiguous; out may be x0 (in place).  tab_a / tab_b f32 device tables of ntab entries; t int64
+ *   [B] on the device, an INDEX into the tables (not a timestep).  16-byte loads / stores when n % 4 == 0 and x0, noise, out
+ *   are 16-byte aligned, one element per thread otherwise (misaligned views are fine).
+ * The kernel clamps t[b] into [0, ntab): a bad index reads a valid entry, never out of bounds (callers validate t first).
+ * PM_E_NULL for a NULL operand, PM_E_SHAPE for B < 1, n < 1 or ntab < 1.
+ */
+int pm_q_sample(const float* x0, const float* noise, const int64_t* t, const float* tab_a, const float* tab_b, float* out,
+                int64_t B, int64_t n, int64_t ntab, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * pm_timestep_embedding: the sinusoidal timestep / fps embedding, y[i, j] = cos(t[i] * freqs[j]), y[i, half + j] =
  * sin(t[i] * freqs[j]) (f32 product, f32 cos / sin), j < half.  replaces timestep_embedding (utils_diffusion.py:8-28) in front
  * of time_embed / fps_embedding (openaimodel3d.py:554-581): the caller passes the reference's frequency table (its bf16-

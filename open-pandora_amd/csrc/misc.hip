@@ -63,6 +63,44 @@ __global__ __launch_bounds__(256) void ddim_kernel(const float* __restrict__ x,
   }
 }
 
+// Forward noising of B clips to a table index each (DDIMSampler.stochastic_encode, ddim.py:314-328; the same expression as
+// q_sample, ddpm3d.py:301-304):  out[b, i] = tab_a[t[b]] * x0[b, i] + tab_b[t[b]] * noise[b, i].  Two products, each rounded
+// to f32, then the sum, rounded - the reference's three separate f32 operations, so the result equals torch's bit for bit:
+// contraction into an FMA is switched off for this function (HIP's __fmul_rn / __fadd_rn are plain `*` / `+` to the compiler).
+// VEC: one 16-byte load of x0 and noise and one 16-byte store per thread (n % 4 == 0 and all three operands 16-byte aligned:
+// then every clip starts aligned); else one element per thread.  The index is clamped into [0, ntab) here (the host wrapper
+// rejects such values before the launch), so no index can make the kernel read outside the tables.  out may be x0: every
+// thread reads its elements before it writes them and no other thread touches them (no __restrict__ on the two).
+template <bool VEC>
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const float* __restrict__ noise,
+                                                       const long long* __restrict__ t, const float* __restrict__ tab_a,
+                                                       const float* __restrict__ tab_b, float* out, int64_t B, int64_t n,
+                                                       int64_t ntab) {
+#pragma clang fp contract(off)
+  const int64_t per = VEC ? n / 4 : n;
+  const int64_t total = B * per;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / per;
+    long long ti = t[b];
+    ti = ti < 0 ? 0 : (ti >= ntab ? ntab - 1 : ti);
+    const float a = tab_a[ti], s = tab_b[ti];
+    if (VEC) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + i * 4);
+      const f32x4 nv = *reinterpret_cast<const f32x4*>(noise + i * 4);
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float p = a * xv[e], q = s * nv[e];
+        o[e] = p + q;
+      }
+      *reinterpret_cast<f32x4*>(out + i * 4) = o;
+    } else {
+      const float p = a * x0[i], q = s * noise[i];
+      out[i] = p + q;
+    }
+  }
+}
+
 // y[f, p, c] = c < C1 ? x[c, f, p] : cond[c - C1, f, p]      (C1 + C2 is small: 8)
 template <typename T>
 __global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict__ x,
@@ -361,6 +399,25 @@ extern "C" int pm_ddim_update(const float* x, const void* e_c, const void* e_u, 
                                        x_prev, pred_x0, n, cfg, sqrt_ac, sqrt_1mac, rescale,
                                        sqrt_a_prev, dir_coef, sigma);
                     return check_launch());
+}
+
+extern "C" int pm_q_sample(const float* x0, const float* noise, const int64_t* t, const float* tab_a, const float* tab_b,
+                           float* out, int64_t B, int64_t n, int64_t ntab, void* stream) {
+  if (!x0 || !noise || !t || !tab_a || !tab_b || !out) return PM_E_NULL;
+  if (B < 1 || n < 1 || ntab < 1) return PM_E_SHAPE;
+  const bool vec = (n & 3) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const int64_t total = B * (vec ? n / 4 : n);
+  int64_t nb = (total + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  const long long* tp = reinterpret_cast<const long long*>(t);
+  if (vec)
+    hipLaunchKernelGGL((q_sample_kernel<true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x0, noise, tp, tab_a,
+                       tab_b, out, B, n, ntab);
+  else
+    hipLaunchKernelGGL((q_sample_kernel<false>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x0, noise, tp, tab_a,
+                       tab_b, out, B, n, ntab);
+  return check_launch();
 }
 
 namespace pm {

@@ -12,6 +12,9 @@ guidance_rescale, **kwargs)` -> (samples, intermediates), including the gradio p
 * all per-step scalars are computed once on the host with the reference's exact arithmetic
   (bf16-quantised tables, f64 sigmas cast to f32, f32 `1 - a_prev - sigma^2`), so the reference's
   numerics quirks are reproduced, including the NaN of S=10 / eta=1 / 'uniform_trailing' (SURVEY §0.5);
+* `stochastic_encode` / `decode` (ddim.py:292-328), the img2img pair that starts from a given latent instead of pure noise, and
+  the `timesteps=` subset of `ddim_sampling` run on the same step: the noising is one kernel (pm_q_sample), the partial loop is
+  p_sample_ddim.  The original-step (1000-step) variants of the loops raise: the reference's own result is non-finite there;
 * noise comes from an injectable `noise_fn(step_index, shape) -> f32 tensor` (default: torch.randn
   on the device), so both sides of a parity run can consume the same draws.
 """
@@ -21,6 +24,13 @@ import numpy as np
 import torch
 
 _CAPTURE_STREAMS = {}
+
+# decode(use_original_steps=True) / ddim_sampling(ddim_use_original_steps=True), ddim.py:252-256,296
+_ORIGINAL_STEPS = ("the 1000-step (original DDPM steps) trajectory is not built: the reference's own result is non-finite on this "
+                   "fork's bf16 schedule buffers - alphas_cumprod[0] rounds to 1.0, so ddim_sigmas_for_original_num_steps[0] is "
+                   "0 / 0 (ddim.py:60-62) and every such trajectory ends at index 0; with use_dynamic_rescale it also reads "
+                   "ddim_scale_arr[index], a table of S entries - there is nothing finite to compare against.  "
+                   "stochastic_encode(use_original_steps=True) is finite in the reference and is available")
 
 
 def _capture_streams(dev):
@@ -32,6 +42,17 @@ def _capture_streams(dev):
     if key not in _CAPTURE_STREAMS:
         _CAPTURE_STREAMS[key] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
     return _CAPTURE_STREAMS[key]
+
+
+def _sqrt_f32(x):
+    """The correctly rounded f32 square root of every entry of an f32 host tensor - what torch.sqrt / np.sqrt of that tensor
+    give on a host whose vector square root is IEEE-exact, and what the reference's fixtures therefore hold.  Not torch.sqrt
+    itself: its vectorised CPU kernel was measured one ulp off on one host (sqrt(0x1.c6p-1) = 0x1.e220eep-1 for the exact
+    0x1.e220ecp-1, 4 of the 10 entries of an S = 10 table), and stochastic_encode is held to bit equality.  The scalar f64
+    square root of the C library is exact everywhere, and rounding it to f32 is the exact f32 result (a 53-bit square root
+    rounded to 24 bits cannot double-round: 53 >= 2 x 24 + 2)."""
+    import math
+    return torch.tensor([math.sqrt(v) for v in x.to(torch.float64).tolist()], dtype=torch.float64).to(torch.float32)
 
 
 def make_ddim_timesteps(method, num_ddim, num_ddpm):
@@ -295,6 +316,7 @@ class DDIMSampler:
         self._seg_failed = False  # the frame group decided against segmented replay (or, at one rank, a capture raised)
         self._seg_probed = False
         self._gen = None  # multi-rank noise generator (see _draw)
+        self._enc_tables = {}  # stochastic_encode's device tables (see make_schedule)
 
     def close(self, twin=True):
         """Release every captured graph of this sampler: the device drains, the graphs, the exchange closures recorded
@@ -374,6 +396,7 @@ class DDIMSampler:
             self.ddim_scale_arr_prev = torch.cat([sa[0:1], sa[:-1]])
         self._sqrt_ac = m.sqrt_alphas_cumprod.detach().to(torch.float32).cpu().numpy()
         self._sqrt_1mac = m.sqrt_one_minus_alphas_cumprod.detach().to(torch.float32).cpu().numpy()
+        self._enc_tables = {}  # stochastic_encode's device tables: formed on first use, dropped with the schedule
 
     def step_scalars(self, index, step):
         """f32 scalars of p_sample_ddim (ddim.py:252-288) for the fused update kernel: v- and eps-parameterisation."""
@@ -615,7 +638,11 @@ class DDIMSampler:
                       log_every_t=100, temperature=1.0, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, verbose=True, precision=None, fs=None,
                       noise_fn=None, guidance_rescale=0.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None,
-                      **kwargs):
+                      timesteps=None, ddim_use_original_steps=False, **kwargs):
+        """`timesteps=k` (ddim.py:163-165): only the first `int(min(k / S, 1) * S) - 1` entries of the schedule are walked -
+        the reference's off-by-one kept as it is (k = 6 of S = 10 runs 5 steps)."""
+        if ddim_use_original_steps:
+            raise NotImplementedError(_ORIGINAL_STEPS)
         ops = self._ops()
         device = ops.device
         img = self._draw(shape, device) if x_T is None else x_T.to(device)
@@ -638,7 +665,11 @@ class DDIMSampler:
             if noise_fn is not None:
                 user_noise = noise_fn
                 noise_fn = lambda i, shp: shard(user_noise(i, shape))
-        timesteps = self.ddim_timesteps
+        if timesteps is None:
+            timesteps = self.ddim_timesteps
+        else:
+            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
+            timesteps = self.ddim_timesteps[:subset_end]
         total_steps = timesteps.shape[0]
         time_range = np.flip(timesteps)
         intermediates = {"x_inter": [img], "pred_x0": [img]}
@@ -692,6 +723,100 @@ class DDIMSampler:
         if precision is not None and isinstance(precision, torch.dtype):
             img = img.to(precision)
         return img, intermediates
+
+    def _partial_guard(self, what):
+        if self._multi_rank():
+            raise NotImplementedError(f"{what} runs on one GPU (no frame shards, no CFG pair): the ranks of one clip would "
+                                      "have to share the encode noise and the start latent")
+        if self.multicond:
+            raise NotImplementedError(f"{what} is the main sampler's (ddim.py); ddim_multiplecond.py has no such path")
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False, callback=None, *, fs=None, noise_fn=None, temperature=1.0, guidance_rescale=0.0,
+               verbose=True, **kwargs):
+        """Denoise `x_latent` from step `t_start` of the current schedule down to the clean latent (ddim.py:292-312): the
+        last `t_start` steps of the DDIM loop, `ddim_timesteps[:t_start]` walked backwards - the second half of the img2img
+        pair `stochastic_encode(x0, [t_start - 1])` -> `decode(z, cond, t_start)`.  The reference's arguments in its order; the
+        keyword-only ones are this sampler's (`noise_fn(i, shape)` as in ddim_sampling; `fs` and **kwargs go to the U-Net - the
+        reference's decode passes neither).  Every step is p_sample_ddim: graph replay, the two CFG streams and
+        PANDORA_CFG_BATCH apply as in `sample`, and a decode on the tensors a `sample` ran on replays its graph."""
+        if use_original_steps:
+            raise NotImplementedError(_ORIGINAL_STEPS)
+        self._partial_guard("decode")
+        total_steps = int(self.ddim_timesteps.shape[0])
+        if not 1 <= int(t_start) <= total_steps:
+            raise ValueError(f"decode: t_start={t_start} outside [1, {total_steps}] (the schedule's step count)")
+        device = self._ops().device
+        timesteps = self.ddim_timesteps[:int(t_start)]
+        time_range = np.flip(timesteps)
+        total_steps = timesteps.shape[0]
+        if verbose:
+            from tqdm import tqdm
+            iterator = tqdm(time_range, desc="Decoding image", total=total_steps)
+        else:
+            iterator = time_range
+        x_dec = x_latent.to(device=device, dtype=torch.float32).contiguous()  # the loop state stays f32 (see module docstring)
+        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        if fs is None and getattr(unet, "fs_condition", False) and hasattr(unet, "default_fs"):
+            # the reference's call: no fs, the U-Net falls back to its default_fs (openaimodel3d.py:574-577).  Ours would build that
+            # tensor inside every forward - a host-to-device copy, which a graph capture cannot hold - so it is built here, once
+            fs = torch.tensor([unet.default_fs], dtype=torch.long, device=device)
+        shape = tuple(x_dec.shape)
+        for i, step in enumerate(iterator):
+            index = total_steps - i - 1
+            step = int(step)
+            ts = torch.full((shape[0],), step, device=device, dtype=torch.long)
+            noise = noise_fn(i, shape) if noise_fn is not None else None
+            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index, temperature=temperature,
+                                          unconditional_guidance_scale=unconditional_guidance_scale,
+                                          unconditional_conditioning=unconditional_conditioning, fs=fs, noise=noise,
+                                          want_x0=False, step=step, guidance_rescale=guidance_rescale, **kwargs)
+            if callback:
+                callback(i)
+        return x_dec
+
+    def _encode_tables(self, use_original_steps, device):
+        """(sqrt(a), sqrt(1 - a)) f32 on `device`, the values the reference forms on the host (ddim.py:318-323, :59): the f32
+        square roots of the f32 `ddim_alphas` and of the f32 `1 - ddim_alphas` (_sqrt_f32), or - `use_original_steps` - the f32
+        copies of the model's 1000-entry bf16 buffers (:46-47).  Cached until the next make_schedule."""
+        key = (bool(use_original_steps), str(device))
+        if key not in self._enc_tables:
+            if use_original_steps:
+                m = self.model
+                a = m.sqrt_alphas_cumprod.detach().to(torch.float32).cpu()
+                s = m.sqrt_one_minus_alphas_cumprod.detach().to(torch.float32).cpu()
+            else:
+                a, s = _sqrt_f32(self.ddim_alphas), _sqrt_f32(1.0 - self.ddim_alphas)
+            self._enc_tables[key] = (a.contiguous().to(device), s.to(torch.float32).contiguous().to(device))
+        return self._enc_tables[key]
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """Noise the clean latent `x0` (b, ...) to step t[b] of the current schedule in one jump (ddim.py:314-328):
+        sqrt(a_t) x0 + sqrt(1 - a_t) noise, f32.  `t` (b,) INDEXES the tables - positions in `ddim_timesteps`, or DDPM
+        timesteps with `use_original_steps` - it is not a timestep otherwise.  An index outside the table is a ValueError.
+        On an op table with `q_sample` (HipOps: pm_q_sample) this is one kernel launch; otherwise the reference's expression
+        in torch.  Either way the result equals the reference's bit for bit."""
+        self._partial_guard("stochastic_encode")
+        ops = self._ops()
+        device = ops.device
+        tab_a, tab_s = self._encode_tables(use_original_steps, device)
+        t = torch.as_tensor(t, dtype=torch.long).reshape(-1)
+        x0 = x0.to(device=device, dtype=torch.float32).contiguous()
+        if t.shape[0] != x0.shape[0]:
+            raise ValueError(f"stochastic_encode: {t.shape[0]} indices for {x0.shape[0]} clips (one per clip)")
+        noise = self._draw(tuple(x0.shape), device) if noise is None else noise
+        noise = noise.to(device=device, dtype=torch.float32).contiguous()
+        q_sample = getattr(ops, "q_sample", None)
+        if q_sample is not None:
+            return q_sample(x0, noise, t, tab_a, tab_s)
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi >= tab_a.numel():
+            raise ValueError(f"stochastic_encode: indices span [{lo}, {hi}], the tables have {tab_a.numel()} entries")
+        idx = t.to(tab_a.device)
+        view = (-1,) + (1,) * (x0.dim() - 1)
+        return tab_a[idx].view(view) * x0 + tab_s[idx].view(view) * noise
 
 
 class DDIMSamplerMultiCond(DDIMSampler):

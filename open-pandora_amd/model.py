@@ -131,6 +131,17 @@ class WorldModel:
             guidance_rescale=guidance_rescale, **kwargs)
 
     @torch.no_grad()
+    def image_guided_refinement(self, diffusion_conditioning, videos, diffusion_cond_image, init, strength, ddim_steps=50,
+                                ddim_eta=1., unconditional_guidance_scale=1.0, fs=None, timestep_spacing='uniform',
+                                guidance_rescale=0.0, n_samples=1, **kwargs):
+        """img2img from a given clip (`init`: latent or frames) through the sampler's stochastic_encode -> decode
+        (ddim.py:292-328); the reference's model.py has no caller of that pair - see wm.DiffusionRunner.image_guided_refinement."""
+        return self.runner.image_guided_refinement(
+            diffusion_conditioning, videos, diffusion_cond_image, init, strength, ddim_steps=ddim_steps, ddim_eta=ddim_eta,
+            unconditional_guidance_scale=unconditional_guidance_scale, fs=fs, timestep_spacing=timestep_spacing,
+            guidance_rescale=guidance_rescale, n_samples=n_samples, **kwargs)
+
+    @torch.no_grad()
     def generate(self, input_ids, pixel_values=None, diffusion_pixel_values=None, diffusion_cond_image=None,
                  attention_mask=None, tokenizer=None, **generate_kwargs):
         """model.py:783-816: batch size 1; the prompt must end in the image-prefix token; only the LAST conditioning row is

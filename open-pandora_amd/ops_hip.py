@@ -800,6 +800,27 @@ class HipOps:
         capi.check(rc, "pm_ddim_update")
         return x_prev, x0
 
+    def q_sample(self, x0, noise, t, tab_a, tab_b, out=None):
+        """out[b] = tab_a[t[b]] * x0[b] + tab_b[t[b]] * noise[b] (pm_q_sample): x0 / noise f32 (B, ...) dense (views at any
+        element offset are fine), t int64 (B,) of table INDICES, tab_a / tab_b f32 device tables of equal length; out may be
+        x0.  An index outside the tables is a ValueError here, before the launch (the kernel would clamp it); checked where
+        `t` lives, so a host-side `t` costs no device sync."""
+        B, ntab = x0.shape[0], tab_a.numel()
+        assert x0.dtype == noise.dtype == torch.float32 and x0.shape == noise.shape and x0.is_contiguous() and noise.is_contiguous()
+        assert tab_a.dtype == tab_b.dtype == torch.float32 and tab_b.numel() == ntab and tab_a.is_contiguous() and tab_b.is_contiguous()
+        assert t.dtype == torch.int64 and t.shape == (B,)
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi >= ntab:
+            raise ValueError(f"q_sample: indices span [{lo}, {hi}], the tables have {ntab} entries")
+        t = t.to(self.device).contiguous()
+        if out is None:
+            out = torch.empty_like(x0)
+        assert out.dtype == torch.float32 and out.shape == x0.shape and out.is_contiguous()
+        rc = self.lib.pm_q_sample(_ptr(x0), _ptr(noise), _ptr(t), _ptr(tab_a), _ptr(tab_b), _ptr(out), B, x0.numel() // B, ntab,
+                                  self._stream())
+        capi.check(rc, f"pm_q_sample B={B} n={x0.numel() // B} ntab={ntab}")
+        return out
+
     def pack_input(self, x, cond):
         """x f32 [C1, F, P], cond f32 [C2, F, P] -> [F*P, C1+C2] activations."""
         C1, F, P = x.shape

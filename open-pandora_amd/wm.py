@@ -4,6 +4,8 @@ world-model driver (model.py), restated around the MI355X path:
   DiffusionRunner.image_guided_synthesis(...)   model.py:703-781   the reference's argument list (condition
                                 assembly from `videos` / `diffusion_cond_image`, n_samples loop, sampler call);
                                 `_synthesize` is the factored core on already-embedded conditions
+  DiffusionRunner.image_guided_refinement(...)  (no caller in the reference) the same conditions around the sampler's
+                                img2img pair, ddim.py:292-328: noise a given clip to step k, denoise from k
   get_latent_z(...)             model.py:690-701   conditioning-frame tiling to 16 latent frames
   DiffusionRunner.generate(...) model.py:783-816   noise_shape from the conditioning frames
   multi-round stitching         model.py:1094-1129, 1199-1211
@@ -33,6 +35,22 @@ def get_latent_z(encode_first_stage, videos):
     return repeat(z, "b c t h w -> b c (repeat t) h w", repeat=4)
 
 
+def _condition_sets(diffusion_conditioning, img_emb, uc_text_emb, uc_img_emb, z_cond, batch_size, fs,
+                    unconditional_guidance_scale, cfg_img=None, multiple_cond_cfg=False):
+    """The sampler's condition dictionaries from embedded conditions (model.py:713-743) -> (fs tensor, cond, uc, uc_2)."""
+    dev = z_cond.device
+    fs = torch.tensor([fs] * batch_size, dtype=torch.long, device=dev)
+    cond = {"c_crossattn": [torch.cat([diffusion_conditioning, img_emb], dim=1)], "c_concat": [z_cond]}
+    uc = None
+    if unconditional_guidance_scale != 1.0:
+        uc = {"c_crossattn": [torch.cat([uc_text_emb, uc_img_emb], dim=1)], "c_concat": [z_cond]}
+    # model.py:736-743: one more unconditional set - image tokens kept, text empty - for the multi-condition sampler
+    uc_2 = None
+    if multiple_cond_cfg and cfg_img != 1.0 and unconditional_guidance_scale != 1.0:
+        uc_2 = {"c_crossattn": [torch.cat([uc_text_emb, img_emb], dim=1)], "c_concat": [z_cond]}
+    return fs, cond, uc, uc_2
+
+
 @torch.no_grad()
 def _synthesize(diffusion_model, diffusion_conditioning, img_emb, uc_text_emb, uc_img_emb, z_cond,
                 noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.0,
@@ -53,16 +71,8 @@ def _synthesize(diffusion_model, diffusion_conditioning, img_emb, uc_text_emb, u
             twin.close()  # one graph pool (a forward's activations per branch) alive at a time
     sampler = sampler or DDIMSampler(diffusion_model)
     batch_size = noise_shape[0]
-    dev = z_cond.device
-    fs = torch.tensor([fs] * batch_size, dtype=torch.long, device=dev)
-    cond = {"c_crossattn": [torch.cat([diffusion_conditioning, img_emb], dim=1)], "c_concat": [z_cond]}
-    uc = None
-    if unconditional_guidance_scale != 1.0:
-        uc = {"c_crossattn": [torch.cat([uc_text_emb, uc_img_emb], dim=1)], "c_concat": [z_cond]}
-    # model.py:736-743: one more unconditional set - image tokens kept, text empty - for the multi-condition sampler
-    uc_2 = None
-    if multiple_cond_cfg and cfg_img != 1.0 and unconditional_guidance_scale != 1.0:
-        uc_2 = {"c_crossattn": [torch.cat([uc_text_emb, img_emb], dim=1)], "c_concat": [z_cond]}
+    fs, cond, uc, uc_2 = _condition_sets(diffusion_conditioning, img_emb, uc_text_emb, uc_img_emb, z_cond, batch_size, fs,
+                                         unconditional_guidance_scale, cfg_img, multiple_cond_cfg)
     kwargs.update({"unconditional_conditioning_img_nonetext": uc_2})
     variants = []
     try:
@@ -150,6 +160,18 @@ class DiffusionRunner:
         self._uncond_text_fn = value if lazy else None
         self._uncond_text_emb = None if lazy else value
 
+    def _embed_conditions(self, videos, diffusion_cond_image, unconditional_guidance_scale):
+        """-> (c_concat latent, image tokens, unconditional text tokens, unconditional image tokens) (model.py:710-729)."""
+        z = get_latent_z(self.encode_first_stage, videos)
+        img_emb = self.embed_image(diffusion_cond_image)
+        uc_text = uc_img_emb = None
+        if unconditional_guidance_scale != 1.0:
+            uc_text = self.uncond_text_emb  # uncond_type "empty_seq": the text encoder's tokens of "" (:723-725)
+            uncond = getattr(self.embed_image, "uncond", None)  # ImageContext caches the zero-image tokens
+            uc_img_emb = (uncond(diffusion_cond_image) if uncond
+                          else self.embed_image(torch.zeros_like(diffusion_cond_image)))
+        return z, img_emb, uc_text, uc_img_emb
+
     @torch.no_grad()
     def image_guided_synthesis(self, diffusion_conditioning, videos, diffusion_cond_image, noise_shape, n_samples=1,
                                ddim_steps=50, ddim_eta=1., unconditional_guidance_scale=1.0, cfg_img=None, fs=None,
@@ -162,20 +184,71 @@ class DiffusionRunner:
         `gfi` are accepted and unused, exactly as in the reference's body (they never reach the sampler there
         either: they are named parameters, not **kwargs).  -> (b, n_samples, c, T, H, W)."""
         del loop, gfi
-        z = get_latent_z(self.encode_first_stage, videos)
-        img_emb = self.embed_image(diffusion_cond_image)
-        uc_text = uc_img_emb = None
-        if unconditional_guidance_scale != 1.0:
-            uc_text = self.uncond_text_emb  # uncond_type "empty_seq": the text encoder's tokens of "" (:723-725)
-            uncond = getattr(self.embed_image, "uncond", None)  # ImageContext caches the zero-image tokens
-            uc_img_emb = (uncond(diffusion_cond_image) if uncond
-                          else self.embed_image(torch.zeros_like(diffusion_cond_image)))
+        z, img_emb, uc_text, uc_img_emb = self._embed_conditions(videos, diffusion_cond_image, unconditional_guidance_scale)
         return _synthesize(self.diffusion_model, diffusion_conditioning, img_emb, uc_text, uc_img_emb, z, noise_shape,
                            n_samples=n_samples, ddim_steps=ddim_steps, ddim_eta=ddim_eta,
                            unconditional_guidance_scale=unconditional_guidance_scale, cfg_img=cfg_img, fs=fs,
                            multiple_cond_cfg=multiple_cond_cfg, timestep_spacing=timestep_spacing,
                            guidance_rescale=guidance_rescale, sampler=self.sampler,
                            decode_first_stage=self.decode_first_stage, **kwargs)
+
+    ENCODE_CHUNK = 4  # frames per encode_first_stage call: the encoder addresses its operands with 32-bit byte offsets
+
+    def _init_latent(self, init):
+        """`init` as a scaled latent (b, 4, T, h, w): a latent is taken as it is, frames (b, 3, T, H, W) go through
+        encode_first_stage at most ENCODE_CHUNK frames per call (16 frames of 576x1024 in one call overflow the encoder's
+        32-bit operand offsets; it does not chunk itself)."""
+        if init.dim() != 5 or init.shape[1] not in (3, 4):
+            raise ValueError(f"init: want a latent (b, 4, T, h, w) or frames (b, 3, T, H, W), got {tuple(init.shape)}")
+        if init.shape[1] == 4:
+            return init
+        b, c, t, h, w = init.shape
+        flat = init.permute(0, 2, 1, 3, 4).reshape(b * t, c, h, w)
+        z = torch.cat([self.encode_first_stage(flat[i:i + self.ENCODE_CHUNK]) for i in range(0, b * t, self.ENCODE_CHUNK)], 0)
+        return z.reshape(b, t, *z.shape[1:]).permute(0, 2, 1, 3, 4)
+
+    @torch.no_grad()
+    def image_guided_refinement(self, diffusion_conditioning, videos, diffusion_cond_image, init, strength, ddim_steps=50,
+                                ddim_eta=1.0, unconditional_guidance_scale=1.0, fs=None, timestep_spacing="uniform",
+                                guidance_rescale=0.0, n_samples=1, **kwargs):
+        """img2img / SDEdit on a clip: start from `init` - a scaled latent (b, 4, T, h, w) or frames (b, 3, T, H, W), e.g. a
+        previous round, a user video, a draft of a cheaper configuration - instead of pure noise; conditions as for
+        `image_guided_synthesis` (same condition assembly).  The original latent-diffusion img2img convention:
+            t_enc = int(strength * ddim_steps), clamped to [1, ddim_steps]     (strength 0: one step, 1: the whole schedule)
+            make_schedule(ddim_steps, timestep_spacing, ddim_eta)
+            z = stochastic_encode(init, full((b,), t_enc - 1))                 (DDIMSampler, ddim.py:314-328)
+            samples = decode(z, cond, t_enc, scale, uc)                        (ddim.py:292-312)
+        stochastic_encode takes an INDEX into the schedule and decode a step COUNT: `t_enc - 1` is the index of the last of the
+        t_enc steps decode keeps, so the decode starts exactly at the step the latent was noised to.  `n_samples` independent
+        encode draws.  Keyword extras: `encode_noise` (the encode's noise instead of a draw), `noise_fn` and anything else
+        DDIMSampler.decode takes.  The multi-condition sampler has no such path: `multiple_cond_cfg=True` raises.
+        -> (b, n_samples, c, T, H, W) as image_guided_synthesis: frames if `decode_first_stage` is set, else latents."""
+        if kwargs.pop("multiple_cond_cfg", False):
+            raise NotImplementedError("image_guided_refinement runs the main sampler's stochastic_encode / decode; the "
+                                      "multi-condition sampler (ddim_multiplecond.py) has neither")
+        if fs is None:
+            raise ValueError("image_guided_refinement needs `fs` (the fps / frame-stride condition), as image_guided_synthesis")
+        z_cond, img_emb, uc_text, uc_img_emb = self._embed_conditions(videos, diffusion_cond_image, unconditional_guidance_scale)
+        z_init = self._init_latent(init)
+        batch_size = z_init.shape[0]
+        fs, cond, uc, _ = _condition_sets(diffusion_conditioning, img_emb, uc_text, uc_img_emb, z_cond, batch_size, fs,
+                                          unconditional_guidance_scale)
+        sampler = self.sampler
+        twin = getattr(sampler, "_multicond_twin", None)
+        if twin is not None and twin._graphs:
+            twin.close()  # one graph pool alive at a time, as in _synthesize
+        t_enc = min(max(int(strength * ddim_steps), 1), ddim_steps)
+        sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_discretize=timestep_spacing, ddim_eta=ddim_eta, verbose=False)
+        encode_noise = kwargs.pop("encode_noise", None)
+        verbose = kwargs.pop("verbose", False)
+        variants = []
+        for _ in range(n_samples):
+            z = sampler.stochastic_encode(z_init, torch.full((batch_size,), t_enc - 1, dtype=torch.long), noise=encode_noise)
+            samples = sampler.decode(z, cond, t_enc, unconditional_guidance_scale, uc, fs=fs,
+                                     guidance_rescale=guidance_rescale, verbose=verbose, **kwargs)
+            samples = samples.to(diffusion_conditioning.dtype)  # (as `precision=` of the sampler call in _synthesize)
+            variants.append(self.decode_first_stage(samples) if self.decode_first_stage is not None else samples)
+        return torch.stack(variants).permute(1, 0, 2, 3, 4, 5)
 
     @torch.no_grad()
     def generate(self, diffusion_conditioning, diffusion_pixel_values, diffusion_cond_image, **generate_kwargs):
